@@ -5,7 +5,14 @@ One step = the reference's CFG denoising step (wan_video_new.py:518-542): DiT(40
 and the Euler update.  Synthetic data: random-init weights (N(0,0.02), seed 5), seeded latents /
 contexts / VACE context of the real shapes (no checkpoints or datasets are reachable offline).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`).
+--dump-outputs DIR writes what the last timed step left its caller -- the denoised latents -- as
+DIR/latents.npy (float32); weights and inputs are seeded, so two builds run with the same arguments
+can be compared output for output.  --full adds every measurement that takes a run of its own: the
+self-attention `roofline`, the end-to-end `e2e` components and measured pipeline call, and the
+`cpu_baseline`.
 
 N > 1: one process per GPU, Ulysses SP over all N ranks over RCCL (VSTYLER_OPTS=cfg_parallel=1 selects
 CFG parallelism; sp_comm=native,sp_graph=1 captures the collectives into the step's hipGraph).  Under torchrun (WORLD_SIZE set) WORLD_SIZE must equal N; without a launcher this
@@ -14,8 +21,9 @@ process spawns the N ranks itself (launch_ranks: RANK / LOCAL_RANK / WORLD_SIZE 
 when fewer than N GPUs are visible.  The line carries `rccl_world` and every rank's device and
 ms/step; `n_gpus` is the process group's size.
 
-Prints one JSON line with `roofline` (self-attention kernel, HIP-event timed inside the timed
-region) and, on rank 0 at N=1, `cpu_baseline` (the CPU oracle on a bounded token sample).
+Prints one JSON line; with --full it carries `roofline` (self-attention kernel, HIP-event timed on one
+more step after the graph replays; eager steps carry the events themselves, with or without --full)
+and, on rank 0 at N=1, `e2e` and `cpu_baseline` (the CPU oracle on a bounded token sample).
 """
 import argparse
 import json
@@ -135,6 +143,22 @@ def pmc_traffic(path=os.path.join(os.path.dirname(os.path.abspath(__file__)), "p
         return int(round((rd + wr) * 1e9))
     except (OSError, AttributeError):
         return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, tensors):
+    """--dump-outputs: every tensor as path/<name>.npy in float32 -- whole while all of them fit in
+    DUMP_LIMIT_BYTES, else the same seeded sample of each one's elements on every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // 4 // len(tensors)
+    for name, t in tensors.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > budget:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, budget, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def e2e_components(dev, frames, height, width, step_s, steps=50):
@@ -315,6 +339,11 @@ def main():
     ap.add_argument("--frames", type=int, default=73)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=832)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the attention roofline, the end-to-end "
+                         "components and pipeline call, the CPU baseline (trimmed by the --no-* options)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's result (the latents) to DIR/latents.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-rows", type=int, default=2048)
     ap.add_argument("--no-graph", action="store_true", help="eager steps instead of hipGraph replay")
@@ -326,6 +355,8 @@ def main():
                     help="bf16: BASELINE config (50-step Euler, CFG 5); fp8: config 5 (fp8 block linears, "
                          "UniPC, CFG 1.2, shift 2, SLG block 2, VACE strength 0.975)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no external launcher: this process only spawns the ranks (it never touches the GPU)
@@ -397,11 +428,13 @@ def main():
         TIMER.reset()
         TIMER.enabled = True
         t0 = time.perf_counter()
-        pipe.denoise_unipc(latents, ctx[0:1], ctx[1:2], vc, num_inference_steps=args.steps, **kw)
+        result = pipe.denoise_unipc(latents, ctx[0:1], ctx[1:2], vc, num_inference_steps=args.steps, **kw)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"latents": result})
     else:
         sched = FlowMatchScheduler(shift=5, sigma_min=0.0, extra_one_step=True)
         n_total = args.warmup + args.steps
@@ -442,7 +475,9 @@ def main():
         if world > 1:
             dist.barrier()
         elapsed = time.perf_counter() - t0
-        if use_graph:
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"latents": latents})     # the steps update them in place
+        if use_graph and args.full:
             # ROCm refuses event nodes inside a graph: time the attention launches on one instrumented
             # eager step of the same workload right after the timed replays
             TIMER.enabled = True
@@ -471,8 +506,9 @@ def main():
     # self-attention: 4*S_q*S_kv*d per head and sample, recorded per launch (vstyler.models.attn_flops):
     # one launch per block holds both CFG samples and all heads at SP=1; under Ulysses SP a rank's
     # launch holds H/p heads, one sample per launch with the micro-batch overlap
+    # (timed only with --full when the steps are graph replays: a plain run then has no roofline)
     achieved = attn_tf
-    attn_flops = achieved * 1e12 * attn_ms / 1000
+    attn_flops = achieved * 1e12 * attn_ms / 1000 if attn_n else None
     out = {
         "metric": f"denoising steps/sec, Wan2.1-VACE-{args.model} {args.width}x{args.height}x{args.frames}"
                   + (" [config 5: fp8 e4m3 block linears, UniPC, CFG 1.2, SLG]" if args.config == "fp8" else ""),
@@ -496,7 +532,7 @@ def main():
         "ranks": ranks_info,
         "model_tflops_per_step": round(fl_step / 1e12, 1),
         "mfu_bf16": round(fl_step * value / world / 1e12 / PEAK_BF16_TFLOPS, 4),
-        "roofline": {"kernel": "attn_fwd_w4 (self-attention)", "bound": "mfma",
+        "roofline": None if not attn_n else {"kernel": "attn_fwd_w4 (self-attention)", "bound": "mfma",
                      "achieved": round(achieved, 1), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
                      "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
                      # the committed PMC measurement is of the default workload (14B 832x480x73)
@@ -508,13 +544,13 @@ def main():
                                "timed hipGraph replays" if use_graph else "every launch of the timed steps"),
                      "flops_per_launch": round(attn_flops, -6)},
     }
-    if world == 1 and not args.no_e2e and args.config == "bf16":
+    if args.full and world == 1 and not args.no_e2e and args.config == "bf16":
         out["e2e"] = e2e_components(dev, args.frames, args.height, args.width, elapsed / args.steps)
         if not args.no_e2e_call:
             del stepper
             out["e2e"].update(e2e_measured(dev, dit, vace, ctx, args.frames, args.height, args.width,
                                            t5_s=out["e2e"]["t5_2_prompts_s"]))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(m, S, rows=args.cpu_rows)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -62,8 +62,9 @@ def run_ops():
     w = (1 + 0.1 * torch.randn(D, generator=g)).to(torch.bfloat16)
     freqs = O.rope_freqs(3, 10, 10)
     rn = O.rope_apply(O.rms_norm(x.view(B, S, D), w), freqs, H)
-    np.savez_compressed(os.path.join(HERE, "ops.npz"), q=u16(q), k=u16(k), v=u16(v), attn=u16(o), x=u16(x), w=u16(w),
-                        rmsnorm_rope=u16(rn))
+    # two files: each committed fixture stays under 1 MiB
+    np.savez_compressed(os.path.join(HERE, "ops_attention.npz"), q=u16(q), k=u16(k), v=u16(v), attn=u16(o))
+    np.savez_compressed(os.path.join(HERE, "ops_rmsnorm_rope.npz"), x=u16(x), w=u16(w), rmsnorm_rope=u16(rn))
     print("ops: written")
 
 
@@ -97,7 +98,9 @@ def run_vae480():
     enc, enc64 = both(lambda: V.tiled_encode(video, W, ts, st))
     dec, dec64 = both(lambda: V.tiled_decode(enc, W, ts, st))
     rows = slice(0, None, 8)
-    np.savez_compressed(os.path.join(HERE, "vae_480x832.npz"), enc=u16(enc), dec_rows8=u16(dec[..., rows, :]),
+    # the decode rows in a file of their own: each committed fixture stays under 1 MiB
+    np.savez_compressed(os.path.join(HERE, "vae_480x832_dec.npz"), dec_rows8=u16(dec[..., rows, :]))
+    np.savez_compressed(os.path.join(HERE, "vae_480x832.npz"), enc=u16(enc),
                         noise_enc=np.array(floor(enc64, enc)),
                         noise_dec_rows8=np.array(floor(dec64[..., rows, :], dec[..., rows, :])),
                         video_sum=np.array(video.float().sum().item()),

@@ -14,10 +14,11 @@ def bf(a):
 
 
 def test_ops_fixture():
-    z = np.load(os.path.join(HERE, "ops.npz"))
+    z = np.load(os.path.join(HERE, "ops_attention.npz"))
     q, k, v = bf(z["q"]), bf(z["k"]), bf(z["v"])
     o = O.attention(q, k, v, 2)
     assert (o.float() - bf(z["attn"]).float()).abs().max() <= 2 ** -7
+    z = np.load(os.path.join(HERE, "ops_rmsnorm_rope.npz"))
     x, w = bf(z["x"]), bf(z["w"])
     rn = O.rope_apply(O.rms_norm(x.view(2, 300, 256), w), O.rope_freqs(3, 10, 10), 2)
     assert (rn.float() - bf(z["rmsnorm_rope"]).float()).abs().max() <= 2 ** -6

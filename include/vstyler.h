@@ -124,6 +124,24 @@ int vs_gemm_fp8(const void* a8, long long lda, const float* scale_a, const void*
                 long long ldc, int m, int n, int k, int epilogue, const vs_epilogue* epi, void* stream);
 
 /*
+ * vs_gemm_fp8 with the un-merged (hot-loaded) LoRA term of AutoWrappedLinear.forward on an fp8 layer
+ * (diffsynth/vram_management/layers.py:168-182: out = fp8_linear(x, W, b), then out + x A^T B^T in
+ * bf16) fused as a second, bf16 K phase of the same kernel:
+ *   C = epilogue(s[m] * (A8 . W8^T) + A2[M,K2] . W2[N,K2]^T)
+ * with A2 = x (alpha A)^T (bf16, computed by a previous vs_gemm from the bf16 activation) and W2 = B
+ * (bf16).  The row scale applies to the fp8 product only; both products are accumulated into one
+ * fp32 sum that is rounded to bf16 once (with the bias), then GELU / gate-residual (+ hint) /
+ * residual exactly as vs_gemm_fp8 -- the rounding contract of vs_gemm's LoRA phase: at most one bf16
+ * ulp of the sum from the reference, which rounds the fp8 output and the LoRA term separately.
+ * Every rule of vs_gemm_fp8, and K2 >= 0 with K2 % 64 == 0; with K2 > 0: A2 / W2 non-null, 16-B
+ * aligned, lda2 / ldw2 >= K2 and multiples of 8.  K2 == 0 is vs_gemm_fp8.  With K2 > 0 the launch
+ * always runs the 8-phase fp8 kernel on a whole-tile grid (no split tail, no workspace).
+ */
+int vs_gemm_fp8_lora(const void* a8, long long lda, const float* scale_a, const void* w8, long long ldw,
+                     void* c, long long ldc, int m, int n, int k, int epilogue, const vs_epilogue* epi,
+                     const void* a2, long long lda2, const void* w2, long long ldw2, int k2, void* stream);
+
+/*
  * O = softmax(Q K^T * scale) V per (batch, head), non-causal, no mask.  head_dim must be 128.
  * Q: [batch][sq] rows of stride ldq (head h at columns h*128..), K/V: [batch][skv], O like Q.
  * Replaces flash_attention() / AttentionModule.forward (diffsynth/models/wan_video_dit.py:28-61,

@@ -11,7 +11,8 @@
 // Kernels sharing the epilogue:
 //  * gemm_bf16_tn_8p (K >= 4096 and >= 240 tiles of 256x256): the staggered 8-phase schedule (see
 //    its header) -- the un-merged LoRA second phase and VS_OPT_GEMM_KERNEL 8;
-//  * gemm_fp8_tn_8p: the fp8 (config 5) variant of the same skeleton;
+//  * gemm_fp8_tn_8p: the fp8 (config 5) variant of the same skeleton, with the un-merged LoRA term
+//    after fp8_linear (layers.py:168-182) as a bf16 second K phase (vs_gemm_fp8_lora);
 //  * gemm_bf16_tn (everything else): the structure described below.
 // Structure: 128x128x64 tile, 4 waves (2x2, 64x64 each), v_mfma_f32_16x16x32_bf16 computing the
 // transposed tile (W rows as the A operand) so every lane owns 4 consecutive output columns;
@@ -1316,14 +1317,37 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_tn_4w(
 // as the r2 kernel): lane l holds row l & 31, k = 32 (l >> 5) .. +31 of the k-step, i.e. 16-B chunks
 // 4s + 2(l >> 5) + {0, 1}; chunk swizzle c ^ ((row & 7) ^ ((row >> 3) & 1)) makes these reads
 // conflict-free (the bf16 kernel's c ^ (row & 7) would be 2-way here).
+//
+// LORA: the un-merged LoRA term of AutoWrappedLinear.forward on an fp8 layer (layers.py:168-182:
+// out = fp8_linear(x, W, b), then out + x A^T B^T in bf16) as a second K phase,
+//   C = epilogue(scale_a[m] * (A8 . W8^T) + A2 . W2^T),  A2 [M][K2], W2 [N][K2] bf16, K2 % 64 == 0.
+// A bf16 K-tile is 64 k = the same 128-B rows, so K-tiles nk1 .. nk1 + K2/64 - 1 of the pipeline are
+// staged from A2 / W2 by the same DMA pieces into the same swizzled LDS image, in whichever buffer
+// the tile count lands them (the prologue's second tile included), and read by the SAME fragment
+// reads: a lane's 32 B of k-step s are the 16-B chunks 4s + 2h and 4s + 2h + 1 of its row (h = lane
+// >> 5), i.e. two v_mfma_f32_32x32x16_bf16 operands (8 bf16 each).  The first MFMA takes the low
+// chunk of both operands, the second the high chunk: over the two MFMAs and two k-steps every lane
+// pair (h = 0, 1) covers chunks {4s, 4s+2} then {4s+1, 4s+3}, a permutation of the tile's k applied
+// to both operands alike (a dot product does not care), so no second LDS layout, address set or
+// fragment register is needed and the reads stay the conflict-free 16-B reads of the fp8 tiles
+// (each half alone is a 32-row x 16-B ds_read_b128: the q8_off swizzle gives the 16 lanes of every
+// ds_read_b128 lane group 16 distinct 16-B slots of the 256-B bank row).  Same 32x32 accumulator
+// layout as the MX MFMA, so the phases share the accumulators: at the first LoRA tile every
+// accumulator is multiplied by its row's scale (one scalar per 32x32 tile and lane: the lane's m),
+// the bf16 products accumulate on top in fp32, and the epilogue runs with a unit scale -- one fp32
+// sum, one bf16 rounding (at most 1 bf16 ulp of the sum from the reference's two roundings).
+// No K split with a LoRA phase (whole-tile grid).  WIDE: 16-B epilogue accesses, lanes l and l ^ 32
+// trading 4-column blocks through permlane32_swap (LORA instantiations only).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ int q8_off(int row, int ch) {
     return row * 128 + 16 * (ch ^ (row & 7) ^ ((row >> 3) & 1));
 }
 
+template <bool LORA, bool WIDE>
 __global__ __launch_bounds__(512, 2) void gemm_fp8_tn_8p(
     const uint8_t* __restrict__ A, long long lda, const float* __restrict__ scale_a, const uint8_t* __restrict__ W,
-    long long ldw, bf16_t* C, long long ldc, int M, int N, int K, Epi ep, int ntm, int ntn, int nmain, int ksplit,
+    long long ldw, bf16_t* C, long long ldc, int M, int N, int K, const bf16_t* __restrict__ A2, long long lda2,
+    const bf16_t* __restrict__ W2, long long ldw2, int K2, Epi ep, int ntm, int ntn, int nmain, int ksplit,
     int piece_k, float* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -1340,11 +1364,23 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_tn_8p(
     const int m0 = tm * T8, n0 = tn * T8;
     const int kb = piece < 0 ? 0 : piece * piece_k;
     const int Kp = piece < 0 ? K : min(K - kb, piece_k);
-    const int nt = Kp / 128;
+    const int nk1 = Kp / 128;
+    const int nt = nk1 + ((LORA && piece < 0) ? K2 / 64 : 0);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
+
+    // LORA: the tile's 256 row scales, parked in 1 KB of LDS past the tile buffers until the phase
+    // switch (four registers a lane would otherwise hold across the fp8 K loop, which has none to
+    // spare).  One 4-B LDS-DMA piece per wave 0-3, issued ahead of the prologue's tile DMAs, so the
+    // prologue's counted wait retires it with tile 0.
+    const float* const rscale = reinterpret_cast<const float*>(smem + LDS8);
+    if constexpr (LORA) {
+        if (wave < 4)
+            __builtin_amdgcn_global_load_lds((const GLB_AS void*)(scale_a + min(m0 + tid, M - 1)),
+                                             (LDS_AS void*)(smem + LDS8 + wave * 256), 4, 0, 0);
+    }
 
     f32x16_t acc[2][2][2];
 #pragma unroll
@@ -1372,16 +1408,29 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_tn_8p(
         char* dst = smem + hoff(which, t & 1) + wave * 2048;
         const bool isw = which >= 2;
         const int h = which & 1;
-        const unsigned ko = (unsigned)t * 128u;
         int pr = prow;
         unsigned pc = pcol;
         asm volatile("" : "+v"(pr), "+v"(pc));
+        if (!LORA || t < nk1) {
+            const unsigned ko = (unsigned)t * 128u;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int r = h * 128 + pr + 8 * j;
-            const unsigned pcj = pc ^ (16u * j);
-            const unsigned vo = isw ? (unsigned)min(r, wlim) * (unsigned)ldw + pcj : (unsigned)min(r, alim) * (unsigned)lda + pcj;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(isw ? rw : ra, (LDS_AS void*)(dst + j * 1024), 16, vo, ko, 0, 0);
+            for (int j = 0; j < 2; ++j) {
+                const int r = h * 128 + pr + 8 * j;
+                const unsigned pcj = pc ^ (16u * j);
+                const unsigned vo = isw ? (unsigned)min(r, wlim) * (unsigned)ldw + pcj : (unsigned)min(r, alim) * (unsigned)lda + pcj;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(isw ? rw : ra, (LDS_AS void*)(dst + j * 1024), 16, vo, ko, 0, 0);
+            }
+        } else {
+            // LoRA K-tile t - nk1: 64 bf16 = the same 128-B row pieces and source swizzle, from A2 / W2
+            const unsigned ko = (unsigned)(t - nk1) * 128u;
+            const __amdgpu_buffer_rsrc_t r2 = rsrc(isw ? W2 + (long long)n0 * ldw2 : A2 + (long long)m0 * lda2);
+            const unsigned ld2 = (unsigned)((isw ? ldw2 : lda2) * 2);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int r = h * 128 + pr + 8 * j;
+                const unsigned vo = (unsigned)min(r, isw ? wlim : alim) * ld2 + (pc ^ (16u * j));
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(r2, (LDS_AS void*)(dst + j * 1024), 16, vo, ko, 0, 0);
+            }
         }
     };
 
@@ -1414,13 +1463,28 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_tn_8p(
 #pragma unroll
         for (int s = 0; s < 2; ++s) bf[s] = frag(bbase[s], hoff(region, b) - hoff(R_B0, 0));
     };
-    auto mfma4 = [&](f32x16_t (&c)[2], const i32x8_t (&a)[2][2], const i32x8_t (&bf)[2]) {
+    // the 16-B half (0 low, 1 high chunk) of a 32-B fragment as a 32x32x16 bf16 operand
+    auto half = [](const i32x8_t& v, int hi) {
+        return __builtin_bit_cast(bf16x8_t, i32x4_t{v[4 * hi], v[4 * hi + 1], v[4 * hi + 2], v[4 * hi + 3]});
+    };
+    // lc: the K-tile is a LoRA tile, 8 bf16 MFMAs on the same fragments (see the header)
+    auto mfma4 = [&](f32x16_t (&c)[2], const i32x8_t (&a)[2][2], const i32x8_t (&bf)[2], auto lc) {
         __builtin_amdgcn_s_setprio(1);
+        if constexpr (decltype(lc)::value) {
 #pragma unroll
-        for (int s = 0; s < 2; ++s)
+            for (int s = 0; s < 2; ++s)
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
-                c[i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bf[s], a[i][s], c[i], 0, 0, 0, 0x7f, 0, 0x7f);
+                for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+                        c[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(half(bf[s], hi), half(a[i][s], hi), c[i], 0, 0, 0);
+        } else {
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+                    c[i] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bf[s], a[i][s], c[i], 0, 0, 0, 0x7f, 0, 0x7f);
+        }
         // pin the cluster inside its phase: the IR passes may otherwise sink these register-only
         // MFMAs past the phase's barrier (and keep every fragment set live across phases)
         asm volatile("" : "+v"(c[0]), "+v"(c[1]));
@@ -1450,22 +1514,22 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_tn_8p(
     // waits for the fragments the previous one read, reads the next phase's new ones and runs its 4
     // MX MFMAs under them (the bf16 kernel's stagger measured +-0 here: profiles/r3/
     // gemm_fp8_stagger_ab_s1.log, the 4 MX MFMAs of a phase already cover its reads)
-    auto tile4p = [&](int t, int b, i32x8_t (&b0)[2], i32x8_t (&b0n)[2]) __attribute__((always_inline)) {
+    auto tile4p = [&](int t, int b, i32x8_t (&b0)[2], i32x8_t (&b0n)[2], auto lora) __attribute__((always_inline)) {
         if (t + 1 < nt) stage(t + 1, 1);
         bar_wait_lgkm();
         read_b(b, R_B1, bf1);
         __builtin_amdgcn_sched_barrier(0);
-        mfma4(acc[0][0], af, b0);
+        mfma4(acc[0][0], af, b0, lora);
         bar();
         if (t + 2 < nt) stage(t + 2, 0);
         bar_wait_lgkm();
         read_a(b, R_A1, ag);
         __builtin_amdgcn_sched_barrier(0);
-        mfma4(acc[0][1], af, bf1);
+        mfma4(acc[0][1], af, bf1, lora);
         bar();
         if (t + 2 < nt) stage(t + 2, 2);
         bar_wait_lgkm();
-        mfma4(acc[1][1], ag, bf1);
+        mfma4(acc[1][1], ag, bf1, lora);
         bar();
         if (t + 2 < nt) {
             stage(t + 2, 3);
@@ -1481,15 +1545,43 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_tn_8p(
             read_b(b ^ 1, R_B0, b0n);
         }
         __builtin_amdgcn_sched_barrier(0);
-        mfma4(acc[1][0], ag, b0);
+        mfma4(acc[1][0], ag, b0, lora);
         bar();
+    };
+    // K-tiles [t0, t1) of one phase; the body is written for a pair of tiles so the buffer is a
+    // constant, and a phase that starts on an odd tile (LoRA after an odd fp8 tile count) runs that
+    // tile in buffer 1 first
+    auto run = [&](int t0, int t1, auto lora) __attribute__((always_inline)) {
+        int t = t0;
+        if (t < t1 && (t & 1)) {
+            tile4p(t, 1, bg0, bf0, lora);
+            ++t;
+        }
+#pragma nounroll
+        for (; t < t1; t += 2) {
+            tile4p(t, 0, bf0, bg0, lora);
+            if (t + 1 < t1) tile4p(t + 1, 1, bg0, bf0, lora);
+        }
     };
     read_a(0, R_A0, af);
     read_b(0, R_B0, bf0);
+    if constexpr (!LORA) {
 #pragma nounroll
-    for (int t = 0; t < nt; t += 2) {
-        tile4p(t, 0, bf0, bg0);
-        if (t + 1 < nt) tile4p(t + 1, 1, bg0, bf0);
+        for (int t = 0; t < nt; t += 2) {
+            tile4p(t, 0, bf0, bg0, std::false_type{});
+            if (t + 1 < nt) tile4p(t + 1, 1, bg0, bf0, std::false_type{});
+        }
+    } else {
+        // (K2 > 0 and no K split, host-checked: the switch is unconditional, straight-line code)
+        run(0, nk1, std::false_type{});
+        // phase switch: the fp8 sum takes its row scale, the bf16 products accumulate on top
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int i = 0; i < 2; ++i) acc[a][q][i] *= rscale[128 * a + 64 * wr + 32 * i + frow];
+        run(nk1, nt, std::true_type{});
     }
 
     // acc[qa][qb][i][4g + e] = D[n][m]: m = m0 + 128 qa + 64 wr + 32 i + (lane & 31),
@@ -1510,13 +1602,42 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_tn_8p(
                                     acc[a][b][i][4 * g + 3]};
         return;
     }
+    constexpr bool scaled = LORA;       // (the scale went in at the phase switch)
+    if constexpr (WIDE) {
+        // 16-B epilogue: lanes l and l ^ 32 (same m, column blocks 4 apart) trade one 4-column block of
+        // the block pair (2p, 2p + 1) through permlane32_swap, so a lane of the low half holds columns
+        // 16 p .. + 7 and its partner 16 p + 8 .. + 7: one 8-column epilogue instead of two 4-column ones
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int m = m0 + 128 * a + 64 * wr + 32 * i + frow;
+                const float s = scaled ? 1.f : scale_a[min(m, M - 1)];
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int p = 0; p < 2; ++p) {
+                        float v[8];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float x = acc[a][b][i][8 * p + e], y = acc[a][b][i][8 * p + 4 + e];
+                            const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
+                            v[e] = __uint_as_float(sw[0]) * s;
+                            v[4 + e] = __uint_as_float(sw[1]) * s;
+                        }
+                        const int n = n0 + 128 * b + 32 * wc + 16 * p + 8 * fh;
+                        if (m < M && n < N) epilogue_store_w<8>(v, m, n, C, ldc, ep);
+                    }
+            }
+        return;
+    }
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int m = m0 + 128 * a + 64 * wr + 32 * i + frow;
             if (m >= M) continue;
-            const float sa = scale_a[m];
+            const float sa = scaled ? 1.f : scale_a[m];
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -2196,7 +2317,7 @@ extern "C" int vs_gemm_fp8(const void* a8, long long lda, const float* scale_a, 
     const int tm = (m + BT - 1) / BT, tn = (n + BT - 1) / BT;
     static bool attr8 = false;
     if (!attr8) {
-        (void)hipFuncSetAttribute((const void*)gemm_fp8_tn_8p, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8);
+        (void)hipFuncSetAttribute((const void*)gemm_fp8_tn_8p<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8);
         attr8 = true;
     }
     KSplit sp = plan_ksplit(tm * tn, k / 128, vs_cus_for_split(!vs_opt(VS_OPT_GEMM_SPLIT)), 128);
@@ -2230,9 +2351,10 @@ extern "C" int vs_gemm_fp8(const void* a8, long long lda, const float* scale_a, 
                            (hipStream_t)stream, (const uint8_t*)a8, lda, scale_a, (const uint8_t*)w8, ldw, (bf16_t*)c,
                            ldc, m, n, k, ep, tm, tn, sp.nmain, sp.ksplit, sp.piece_k, part, sc);
     } else
-    hipLaunchKernelGGL(gemm_fp8_tn_8p, dim3((unsigned)(sp.nmain + sp.ntail * sp.ksplit)), dim3(512), LDS8,
+    hipLaunchKernelGGL((gemm_fp8_tn_8p<false, false>), dim3((unsigned)(sp.nmain + sp.ntail * sp.ksplit)), dim3(512), LDS8,
                        (hipStream_t)stream, (const uint8_t*)a8, lda, scale_a, (const uint8_t*)w8, ldw, (bf16_t*)c,
-                       ldc, m, n, k, ep, tm, tn, sp.nmain, sp.ksplit, sp.piece_k, part);
+                       ldc, m, n, k, (const bf16_t*)nullptr, 0LL, (const bf16_t*)nullptr, 0LL, 0, ep, tm, tn, sp.nmain,
+                       sp.ksplit, sp.piece_k, part);
     VS_CHECK_LAUNCH();
     if (sp.ntail) {
         const long long threads = (long long)sp.ntail * BT * (BT / 4);
@@ -2241,6 +2363,41 @@ extern "C" int vs_gemm_fp8(const void* a8, long long lda, const float* scale_a, 
                            sp.ksplit, scale_a);
         VS_CHECK_LAUNCH();
     }
+    return VS_OK;
+}
+
+// vs_gemm_fp8 + the un-merged LoRA term as the fp8 8-phase kernel's second K phase (its header).
+// Always that kernel, whatever VS_OPT_GEMM_KERNEL says (as vs_gemm's LoRA phase), whole-tile grid.
+extern "C" int vs_gemm_fp8_lora(const void* a8, long long lda, const float* scale_a, const void* w8, long long ldw,
+                                void* c, long long ldc, int m, int n, int k, int epilogue, const vs_epilogue* epi,
+                                const void* a2, long long lda2, const void* w2, long long ldw2, int k2, void* stream) {
+    if (k2 < 0 || k2 % 64) return VS_E_INVALID;
+    if (k2 == 0) return vs_gemm_fp8(a8, lda, scale_a, w8, ldw, c, ldc, m, n, k, epilogue, epi, stream);
+    if (!a8 || !scale_a || !w8 || !c || m <= 0 || n <= 0 || k <= 0) return VS_E_INVALID;
+    if (k % 128 || n % 4 || lda < k || ldw < k || ldc < n || (lda & 15) || (ldw & 15) || (ldc & 3))
+        return VS_E_INVALID;
+    if (!aligned16(a8) || !aligned16(w8) || !aligned8(c)) return VS_E_INVALID;
+    if (!a2 || !w2 || lda2 < k2 || ldw2 < k2 || (lda2 & 7) || (ldw2 & 7)) return VS_E_INVALID;
+    if (!aligned16(a2) || !aligned16(w2)) return VS_E_INVALID;
+    Epi ep;
+    const int rc = fill_epi(ep, epilogue, epi, m, n);
+    if (rc) return rc;
+    const int tm = (m + BT - 1) / BT, tn = (n + BT - 1) / BT;
+    static bool attr = false;
+    if (!attr) {
+        for (const void* f : {(const void*)gemm_fp8_tn_8p<true, false>, (const void*)gemm_fp8_tn_8p<true, true>})
+            (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8 + 1024);
+        attr = true;
+    }
+    const bool wide = n % 8 == 0 && ldc % 8 == 0 && aligned16(c) && (!ep.bias || aligned16(ep.bias)) &&
+                      (!ep.res || (ep.ld_res % 8 == 0 && aligned16(ep.res))) &&
+                      (!ep.gate || (ep.gate_bstride % 8 == 0 && aligned16(ep.gate))) &&
+                      (!ep.hint || (ep.ld_hint % 8 == 0 && aligned16(ep.hint)));
+    hipLaunchKernelGGL((wide ? gemm_fp8_tn_8p<true, true> : gemm_fp8_tn_8p<true, false>), dim3((unsigned)(tm * tn)),
+                       dim3(512), LDS8 + 1024, (hipStream_t)stream, (const uint8_t*)a8, lda, scale_a, (const uint8_t*)w8, ldw,
+                       (bf16_t*)c, ldc, m, n, k, (const bf16_t*)a2, lda2, (const bf16_t*)w2, ldw2, k2, ep, tm, tn,
+                       tm * tn, 1, 0, (float*)nullptr);
+    VS_CHECK_LAUNCH();
     return VS_OK;
 }
 

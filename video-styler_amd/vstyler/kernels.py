@@ -176,21 +176,52 @@ def quant_fp8_rows(x, x8, scale):
     return x8, scale
 
 
+def _lora_operands(a2, w2, m, n):
+    """Shape / dtype checks of an un-merged LoRA phase's operands (a2 [m, k2], w2 [n, k2], bf16),
+    on the tensors' metadata alone and before anything else of the call."""
+    if a2 is None or w2 is None:
+        raise ValueError("gemm_fp8: a2 and w2 go together")
+    for t, name in ((a2, "a2"), (w2, "w2")):
+        if t.dtype != BF16:
+            raise ValueError(f"{name}: expected bfloat16, got {t.dtype}")
+        if t.dim() != 2:
+            raise ValueError(f"{name}: expected a 2-D tensor")
+    if a2.shape[0] != m or w2.shape[0] != n or a2.shape[1] != w2.shape[1] or a2.shape[1] % 64:
+        raise ValueError(f"gemm_fp8 LoRA shape mismatch a2={tuple(a2.shape)} w2={tuple(w2.shape)} for out [{m}, {n}] "
+                         f"(rank a multiple of 64)")
+
+
 def gemm_fp8(a8, scale_a, w8, out, epilogue=VS_EPI_BIAS, bias=None, residual=None, gate=None, gate_bstride=0,
-             hint=None, hint_scale=1.0, alpha=1.0, rows_per_batch=0):
-    """out = epilogue(scale_a[m] * (a8 @ w8^T)) with e4m3 operands (see vs_gemm_fp8)."""
+             hint=None, hint_scale=1.0, alpha=1.0, rows_per_batch=0, a2=None, w2=None):
+    """out = epilogue(scale_a[m] * (a8 @ w8^T) (+ a2 @ w2^T)) with e4m3 operands a8 / w8 and the bf16
+    un-merged LoRA phase a2 [M, k2] / w2 [N, k2] (see vs_gemm_fp8, vs_gemm_fp8_lora)."""
+    if a2 is not None or w2 is not None:
+        _lora_operands(a2, w2, a8.shape[0], w8.shape[0])
     M, K, lda = _rows_u8(a8, "a8")
     N, Kw, ldw = _rows_u8(w8, "w8")
     Mo, No, ldc = _rows(out, "out")
     if Kw != K or Mo != M or No != N or scale_a.dtype != torch.float32:
         raise ValueError(f"gemm_fp8 shape mismatch a8={tuple(a8.shape)} w8={tuple(w8.shape)} out={tuple(out.shape)}")
     ep = _epilogue(bias, residual, gate, gate_bstride, hint, hint_scale, alpha, rows_per_batch)
+    k2 = a2.shape[1] if a2 is not None else 0
+    if k2 > 0:                                                          # whole-tile grid, no workspace
+        _, _, lda2 = _rows(a2, "a2")
+        _, _, ldw2 = _rows(w2, "w2")
+        _lib.check(_lib.load().vs_gemm_fp8_lora(a8.data_ptr(), lda, scale_a.data_ptr(), w8.data_ptr(), ldw,
+                                                out.data_ptr(), ldc, M, N, K, int(epilogue), ep, a2.data_ptr(), lda2,
+                                                w2.data_ptr(), ldw2, k2, _stream(a8)))
+        return out
     _split_ws(1, a8)                                                    # split tail of the MFMA kernel
     _split_ws(5, a8)                                                    # its tile queues
     if gemm_route(M, N, K, epilogue=epilogue, fp8=True):                # the A/B build's library route only
         _split_ws(2, a8)
         if epilogue in (VS_EPI_GATE_RES, VS_EPI_RES):
             _split_ws(3, a8, M * N * 2)
+    if a2 is not None:                                                  # an empty LoRA phase: vs_gemm_fp8 by the new entry
+        _lib.check(_lib.load().vs_gemm_fp8_lora(a8.data_ptr(), lda, scale_a.data_ptr(), w8.data_ptr(), ldw,
+                                                out.data_ptr(), ldc, M, N, K, int(epilogue), ep, None, 0, None, 0, 0,
+                                                _stream(a8)))
+        return out
     _lib.check(_lib.load().vs_gemm_fp8(a8.data_ptr(), lda, scale_a.data_ptr(), w8.data_ptr(), ldw, out.data_ptr(),
                                        ldc, M, N, K, int(epilogue), ep, _stream(a8)))
     return out

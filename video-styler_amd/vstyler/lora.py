@@ -8,6 +8,11 @@ hotload_lora : AutoWrappedLinear hot-load (vram_management/layers.py:180-182, pi
                reference's lora_A_weights / lora_B_weights lists, hot-loads accumulate: the padded
                A_i are stacked along the rank rows and the B_i along the rank columns, so several
                adapters stay ONE K phase (sum_i (x A_i^T) B_i^T = (x [A_1; A_2]^T) [B_1 B_2]^T).
+               On a layer converted by quantize_fp8_ (config 5) the same adapter is the fp8 GEMM's
+               bf16 second K phase (hotload_lora(..., fp8_layers="fuse"), vs_gemm_fp8_lora), the
+               reference's out = fp8_linear(x, W, b) + x A^T B^T (layers.py:168-182): the adapter
+               keeps its bf16 precision instead of being rounded into the e4m3 weight, and changing
+               it needs no re-quantisation.  Without that flag an fp8 layer refuses the hot-load.
 """
 import torch
 
@@ -102,12 +107,17 @@ def merge_lora(model, lora, alpha=1.0):
     return updated
 
 
-def hotload_lora(model, lora, alpha=1.0):
+def hotload_lora(model, lora, alpha=1.0, fp8_layers="refuse"):
     """Attach (alpha*A, B) to each matching Linear (layers.py:180-182 appends to the layer's lists);
     an adapter already attached stays and the new one is stacked onto it.  The GEMM adds them all as
-    one fused K phase.  fp8 layers take no hot-loaded LoRA (gap vs the reference's AutoWrappedLinear,
-    layers.py:168-180, which adds the unmerged term after fp8_linear): merge instead.  Every matching
-    module is checked before any is touched, so a refused call leaves the model unchanged."""
+    one fused K phase.  fp8_layers: what to do with matching layers that quantize_fp8_ converted --
+    "refuse" (default): raise and leave the model unchanged (merge the LoRA instead);
+    "fuse": attach to them exactly as to bf16 layers, the adapter staying un-merged in bf16 behind
+    the fp8 GEMM as the reference keeps it (layers.py:168-182; vs_gemm_fp8_lora's second K phase).
+    Every matching module is checked before any is touched, so a refused call leaves the model
+    unchanged."""
+    if fp8_layers not in ("refuse", "fuse"):
+        raise ValueError(f"hotload_lora: fp8_layers must be 'refuse' or 'fuse', got {fp8_layers!r}")
     targets = []
     for name, module in model.named_modules():
         if not isinstance(module, Linear):
@@ -116,7 +126,7 @@ def hotload_lora(model, lora, alpha=1.0):
         if ka in lora and kb in lora:
             targets.append((name, module, ka, kb))
     fp8 = [name for name, module, _, _ in targets if getattr(module, "weight_fp8", None) is not None]
-    if fp8:
+    if fp8 and fp8_layers == "refuse":
         raise NotImplementedError(f"hot-loaded LoRA on fp8 layers ({', '.join(fp8[:3])}"
                                   f"{', ...' if len(fp8) > 3 else ''}): merge the LoRA instead")
     updated = 0

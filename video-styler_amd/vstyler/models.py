@@ -68,17 +68,24 @@ def linear(lin, x, out, ws, **epi):
     the GEMM's second K phase (AutoWrappedLinear, vram_management/layers.py:173-188).  A layer
     converted by quantize_fp8_ runs the fp8 path of AutoWrappedLinear.fp8_linear (:115-151):
     per-row activation quantisation (or the Q8 input ln_into made) + e4m3 MFMA GEMM with the same
-    fused epilogue."""
+    fused epilogue.  A LoRA hot-loaded onto an fp8 layer (hotload_lora(fp8_layers="fuse")) is the fp8
+    GEMM's bf16 second K phase (layers.py:168-182: fp8_linear, then + x A^T B^T): its down-projection
+    reads the bf16 row, so such a layer takes no Q8 input (ln_into hands it bf16 rows)."""
     w8 = getattr(lin, "weight_fp8", None)
     if w8 is not None:
-        if getattr(lin, "lora_A", None) is not None:
-            raise NotImplementedError("hot-loaded LoRA on an fp8 layer: merge the LoRA before quantize_fp8_")
+        la = getattr(lin, "lora_A", None)
         if isinstance(x, Q8):
+            if la is not None:
+                raise ValueError("a quantised activation for an fp8 layer with a hot-loaded LoRA")
             return K.gemm_fp8(x.x8, x.scale, w8, out, bias=lin.bias, **epi)
         M, Kd = x.shape
         x8 = ws.get("fp8_x", (M, Kd), torch.uint8)
         sc = ws.get("fp8_scale", (M,), torch.float32)
         K.quant_fp8_rows(x, x8, sc)
+        if la is not None:
+            t = ws.get("lora_t", (M, la.shape[0]))
+            K.gemm(x, la, t)
+            return K.gemm_fp8(x8, sc, w8, out, bias=lin.bias, a2=t, w2=lin.lora_B, **epi)
         return K.gemm_fp8(x8, sc, w8, out, bias=lin.bias, **epi)
     if isinstance(x, Q8):
         raise ValueError("a quantised activation for a bf16 layer")

@@ -400,11 +400,12 @@ class WanVideoPipeline:
         return pipe
 
     def load_lora(self, module, lora_config=None, alpha=1, hotload=False, state_dict=None):
-        """wan_video_new.py:80-106."""
+        """wan_video_new.py:80-106.  hotload=True on a quantize_fp8_ model keeps the adapter un-merged
+        behind the fp8 GEMMs (layers.py:168-182), as the reference's fp8 workflows do."""
         from .lora import load_lora_state_dict, merge_lora, hotload_lora
         lora = state_dict if state_dict is not None else load_lora_state_dict(lora_config, self.device)
         if hotload:
-            return hotload_lora(module, lora, alpha)
+            return hotload_lora(module, lora, alpha, fp8_layers="fuse")
         return merge_lora(module, lora, alpha)
 
     def enable_vram_management(self, num_persistent_param_in_dit=None, vram_limit=None, vram_buffer=0.5):

@@ -423,6 +423,20 @@ int vs_vace_mask_latents(const void* mask0, void* out, int t, int h, int w, int 
 int vs_unipc_update(float* out, const float* x, const float* m0, const float* m1, const float* mt, long long n,
                     int mode, const float* coef, void* stream);
 
+/* Flow-matching re-noise of clean latents (video-to-video): out = (1 - sigma)*x0 + sigma*noise over n
+ * elements, 1 - sigma taken in fp32.
+ *   fp32 = 0: bf16 tensors, out = bf16(bf16((1 - sigma)*x0) + bf16(sigma*noise)), each product computed
+ *     in fp32 -- FlowMatchScheduler.add_noise (diffsynth/schedulers/flow_match.py:94-100) as torch
+ *     evaluates it on bf16 device tensors with the sigma a 0-d fp32 CPU tensor
+ *     (WanVideoUnit_InputVideoEmbedder, diffsynth/pipelines/wan_video_new.py:591-614).
+ *     n % 8 == 0, 16-byte aligned pointers.
+ *   fp32 = 1: fp32 tensors, every op rounded separately, no contraction -- FlowUniPCMultistepScheduler
+ *     .add_noise (denoising_enhancing/wan/utils/fm_solvers_unipc.py:797-799).  Any n > 0, 4-byte
+ *     aligned pointers.
+ * out may alias x0 or noise.  Any other fp32 value is VS_E_INVALID. */
+int vs_flow_add_noise(const void* x0, const void* noise, void* out, long long n, float sigma, int fp32,
+                      void* stream);
+
 /* Elementwise dtype cast: to_bf16 = 1: fp32 -> bf16 (RNE), 0: bf16 -> fp32. */
 int vs_cast(const void* src, void* dst, long long n, int to_bf16, void* stream);
 

@@ -449,6 +449,35 @@ __global__ void unipc_kernel(float* __restrict__ out, const float* __restrict__ 
     out[i] = base - c3 * res;
 }
 
+// Flow-matching re-noise (video-to-video): out = (1 - sigma)*x0 + sigma*noise.  No __restrict__: out
+// may alias x0 or noise (each thread reads its elements before it writes them).
+//   bf16: out = bf16(bf16(a*x0) + bf16(sigma*noise)), a = 1 - sigma in fp32 -- torch's rounding points
+//         for bf16 tensors times a 0-d fp32 CPU scalar (diffsynth/schedulers/flow_match.py:99)
+__global__ void flow_add_noise_bf16_kernel(const bf16_t* x0, const bf16_t* noise, bf16_t* out, long long n8,
+                                           float sigma) {
+    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (i >= n8) return;
+    const float a = 1.0f - sigma;
+    float xv[8], zv[8];
+    unpack8(reinterpret_cast<const u32x4_t*>(x0)[i], xv);
+    unpack8(reinterpret_cast<const u32x4_t*>(noise)[i], zv);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) xv[e] = rbf(a * xv[e]) + rbf(sigma * zv[e]);
+    reinterpret_cast<u32x4_t*>(out)[i] = pack8(xv);
+}
+
+//   fp32: out = a*x0 + sigma*noise with each op rounded separately (fm_solvers_unipc.py:797-799);
+//         contract(off) for the reason given at unipc_kernel
+__global__ void flow_add_noise_f32_kernel(const float* x0, const float* noise, float* out, long long n, float sigma) {
+#pragma clang fp contract(off)
+    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float a = 1.0f - sigma;
+    const float p = a * x0[i];
+    const float q = sigma * noise[i];
+    out[i] = p + q;
+}
+
 __global__ void cast_kernel(const void* __restrict__ src, void* __restrict__ dst, long long n, int to_bf16) {
     const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -754,6 +783,24 @@ extern "C" int vs_unipc_update(float* out, const float* x, const float* m0, cons
         return VS_E_INVALID;
     hipLaunchKernelGGL(unipc_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, out, x, m0, m1, mt, n,
                        mode, coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+
+extern "C" int vs_flow_add_noise(const void* x0, const void* noise, void* out, long long n, float sigma, int fp32,
+                                 void* stream) {
+    if (!x0 || !noise || !out || n <= 0 || (fp32 != 0 && fp32 != 1)) return VS_E_INVALID;
+    if (fp32) {
+        if ((reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(out)) & 3)
+            return VS_E_INVALID;
+        hipLaunchKernelGGL(flow_add_noise_f32_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                           (const float*)x0, (const float*)noise, (float*)out, n, sigma);
+    } else {
+        if (n % 8 || !al16(x0) || !al16(noise) || !al16(out)) return VS_E_INVALID;
+        const long long n8 = n / 8;
+        hipLaunchKernelGGL(flow_add_noise_bf16_kernel, dim3(nblk(n8, 256)), dim3(256), 0, (hipStream_t)stream,
+                           (const bf16_t*)x0, (const bf16_t*)noise, (bf16_t*)out, n8, sigma);
+    }
     VS_CHECK_LAUNCH();
     return VS_OK;
 }

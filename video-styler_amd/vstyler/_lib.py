@@ -99,6 +99,7 @@ SIGNATURES = {
     "vs_vae_to_u8": [_P, _P, _I, _I, _I, _P],
     "vs_unipc_update": [_P, _P, _P, _P, _P, _LL, _I, ctypes.POINTER(ctypes.c_float), _P],
     "vs_cast": [_P, _P, _LL, _I, _P],
+    "vs_flow_add_noise": [_P, _P, _P, _LL, _F, _I, _P],
     "vs_vace_prepare": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "vs_vace_mask_latents": [_P, _P, _I, _I, _I, _I, _P],
     "vs_vae_tile_blend": [_P, _LL, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],

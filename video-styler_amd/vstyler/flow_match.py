@@ -75,7 +75,15 @@ class FlowMatchScheduler:
         return out
 
     def add_noise(self, original_samples, noise, timestep):
+        """flow_match.py:94-100.  Contiguous bf16 device tensors go through vs_flow_add_noise (torch's
+        rounding points for this expression with the 0-d fp32 CPU sigma); anything else is the
+        reference's torch expression."""
         sigma = self.sigmas[self._index(timestep)]
+        x, z = original_samples, noise
+        if isinstance(x, torch.Tensor) and isinstance(z, torch.Tensor) and x.is_cuda and z.is_cuda \
+                and x.dtype == z.dtype == torch.bfloat16 and x.shape == z.shape and x.device == z.device \
+                and x.is_contiguous() and z.is_contiguous():
+            return K.flow_add_noise(x, z, float(sigma))
         return (1 - sigma) * original_samples + sigma * noise
 
     def training_target(self, sample, noise, timestep):

@@ -372,6 +372,27 @@ def cfg_euler_dev(v_pos, v_neg, x, cfg_scale, dsigma_dev):
     return x
 
 
+def flow_add_noise(x0, noise, sigma, out=None):
+    """(1 - sigma) * x0 + sigma * noise (vs_flow_add_noise): bf16 tensors with torch's bf16 rounding
+    points (flow_match.py:99), fp32 tensors op by op (fm_solvers_unipc.py:797-799).  out may be x0
+    or noise; a new tensor by default."""
+    if x0.dtype != noise.dtype or x0.dtype not in (BF16, torch.float32):
+        raise ValueError(f"flow_add_noise: x0 / noise must both be bfloat16 or both float32, got "
+                         f"{x0.dtype} / {noise.dtype}")
+    if out is None:
+        out = torch.empty_like(x0)
+    for t, n in ((x0, "x0"), (noise, "noise"), (out, "out")):
+        if not t.is_cuda or t.device != x0.device:
+            raise ValueError(f"{n}: expected a tensor on {x0.device}")
+        if t.dtype != x0.dtype or t.shape != x0.shape:
+            raise ValueError(f"{n}: expected {tuple(x0.shape)} {x0.dtype}, got {tuple(t.shape)} {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{n} must be contiguous")
+    _lib.check(_lib.load().vs_flow_add_noise(x0.data_ptr(), noise.data_ptr(), out.data_ptr(), x0.numel(),
+                                             float(sigma), int(x0.dtype == torch.float32), _stream(x0)))
+    return out
+
+
 def time_sinusoid(t, out):
     _lib.check(_lib.load().vs_time_sinusoid(t.data_ptr(), out.data_ptr(), t.numel(), out.shape[-1], _stream(t)))
     return out
@@ -400,6 +421,6 @@ def ulysses_permute(src, dst, batch, s_local, world, cols_per_rank, ld_local, js
     return dst
 
 
-__all__ = ["set_option", "get_option", "options", "ulysses_permute", "gemm", "attention", "layernorm_modulate", "rmsnorm_rope", "patchify", "unpatchify", "cfg_euler",
+__all__ = ["set_option", "get_option", "options", "ulysses_permute", "gemm", "attention", "layernorm_modulate", "rmsnorm_rope", "patchify", "unpatchify", "cfg_euler", "flow_add_noise",
            "time_sinusoid", "mod_add", "axpy", "VS_EPI_BIAS", "VS_EPI_GELU", "VS_EPI_SILU", "VS_EPI_GATE_RES",
            "VS_EPI_RES"]

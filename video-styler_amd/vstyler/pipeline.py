@@ -493,22 +493,40 @@ class WanVideoPipeline:
 
     def denoise_unipc(self, latents, context_posi, context_nega, vace_context=None, vace_scale=1.0,
                       cfg_scale=1.2, num_inference_steps=4, sigma_shift=2.0, slg_blocks=(), slg_range=(0.2, 0.7),
-                      progress_bar_cmd=None):
+                      progress_bar_cmd=None, input_latents=None, forward_step=None, skip_backward_step=None):
         """Config 5's sampler (ditto_comfyui_workflow.json WanVideoSampler 4 / 1.2 / 2.0 / unipc with
         WanVideoSLG): FlowUniPCMultistepScheduler (vstyler.unipc) on fp32 latents, CFG as one
         batch-2 forward, skip-layer guidance on the uncond sample for step fractions in slg_range.
-        CFG combine in bf16 (wan_video_new.py:535 semantics), model input bf16 each step."""
+        CFG combine in bf16 (wan_video_new.py:535 semantics), model input bf16 each step.
+
+        input_latents: the enhancer's re-noise / partial-denoise pass (denoising_enhancing/wan/
+        text2video.py:347-375): `latents` is then the noise, the loop starts from
+        add_noise(input_latents, noise, timesteps[-forward_step]) and runs timesteps[-skip_backward_step:]
+        (both counted from the schedule's end, in [1, n]); a step's SLG fraction stays its index in the
+        full schedule over n."""
         from .unipc import FlowUniPCMultistepScheduler, cast
         sched = FlowUniPCMultistepScheduler(shift=1.0)
         sched.set_timesteps(num_inference_steps, shift=sigma_shift)
+        n = len(sched.timesteps)
+        first = 0
+        if input_latents is None:
+            if forward_step is not None or skip_backward_step is not None:
+                raise ValueError("forward_step / skip_backward_step apply to input_latents=")
+        else:
+            for name, val in (("forward_step", forward_step), ("skip_backward_step", skip_backward_step)):
+                if not isinstance(val, int) or isinstance(val, bool) or not 1 <= val <= n:
+                    raise ValueError(f"{name} must be an integer in [1, {n}], got {val!r}")
+            first = n - skip_backward_step
         use_cfg = cfg_scale != 1.0
         ctx = torch.cat([context_posi, context_nega], 0) if use_cfg else context_posi
         lat32 = latents.to(device=self.device, dtype=torch.float32).contiguous().clone()
+        if input_latents is not None:
+            x0 = input_latents.to(device=self.device, dtype=torch.float32).contiguous()
+            lat32 = sched.add_noise(x0, lat32, sched.timesteps[n - forward_step])
         lat16 = torch.empty(lat32.shape, dtype=BF16, device=self.device)
         v16 = torch.empty(lat32.shape, dtype=BF16, device=self.device)
         v32 = torch.empty_like(lat32)
-        n = len(sched.timesteps)
-        steps = range(n)
+        steps = range(first, n)
         if progress_bar_cmd is not None:
             steps = progress_bar_cmd(steps)
         for i in steps:
@@ -535,12 +553,18 @@ class WanVideoPipeline:
                  sliding_window_size=None, sliding_window_stride=None, tea_cache_l1_thresh=None,
                  tea_cache_model_id="", progress_bar_cmd=None,
                  # extensions of this build (the DiT path without T5/VAE):
-                 prompt_emb=None, negative_prompt_emb=None, vace_context=None, output_type="video", **kwargs):
-        """wan_video_new.py:416-560 for the Ditto path (T2V/VACE, no image/audio/camera inputs)."""
-        for name, val in (("input_image", input_image), ("end_image", end_image), ("input_video", input_video),
+                 prompt_emb=None, negative_prompt_emb=None, vace_context=None, output_type="video",
+                 input_latents=None, **kwargs):
+        """wan_video_new.py:416-560 for the Ditto path (T2V/VACE/video-to-video, no image/audio/camera
+        inputs).  input_video (or its precomputed latents input_latents (1, 16, T', h, w)) with
+        denoising_strength < 1 starts the loop from the video's latents re-noised to the first sigma
+        of the shortened schedule (WanVideoUnit_InputVideoEmbedder, :591-614)."""
+        for name, val in (("input_image", input_image), ("end_image", end_image),
                           ("motion_bucket_id", motion_bucket_id), ("sliding_window_size", sliding_window_size)):
             if val is not None:
                 raise NotImplementedError(f"{name} is outside the Ditto hot path of this build")
+        if input_video is not None and input_latents is not None:
+            raise ValueError("pass input_video or its precomputed input_latents, not both")
         height, width, num_frames = self.check_resize_height_width(height, width, num_frames)
         T = (num_frames - 1) // 4 + 1
         # WanVideoUnit_NoiseInitializer (wan_video_new.py:578-587): f reference images add f latent
@@ -548,9 +572,16 @@ class WanVideoPipeline:
         nref = 0
         if vace_reference_image is not None:
             nref = len(vace_reference_image) if isinstance(vace_reference_image, (list, tuple)) else 1
+        if input_video is not None or input_latents is not None:
+            input_latents = self.encode_input_video(input_video, input_latents, height, width, num_frames, tiled,
+                                                    tile_size, tile_stride, vace_reference_image)
         noise = self.generate_noise((1, 16, T + nref, height // 8, width // 8), seed=seed, rand_device=rand_device)
         if nref:
             noise = torch.cat((noise[:, :, -nref:], noise[:, :, :-nref]), dim=2)
+        start = noise
+        if input_latents is not None:                       # :484, :613: re-noise to the schedule's first sigma
+            self.scheduler.set_timesteps(num_inference_steps, denoising_strength=denoising_strength, shift=sigma_shift)
+            start = self.scheduler.add_noise(input_latents, noise.contiguous(), self.scheduler.timesteps[0])
         if prompt_emb is None:
             prompt_emb = self.encode_prompt(prompt)
         if negative_prompt_emb is None and cfg_scale != 1.0:
@@ -562,7 +593,7 @@ class WanVideoPipeline:
         if tea_cache_l1_thresh is not None:                # WanVideoUnit_TeaCache (:936-947)
             from .teacache import TeaCache
             tea_cache = TeaCache(num_inference_steps, rel_l1_thresh=tea_cache_l1_thresh, model_id=tea_cache_model_id)
-        latents = self.denoise(noise, prompt_emb.to(self.device), None if negative_prompt_emb is None else
+        latents = self.denoise(start, prompt_emb.to(self.device), None if negative_prompt_emb is None else
                                negative_prompt_emb.to(self.device),
                                None if vace_context is None else vace_context.to(self.device), vace_scale,
                                cfg_scale, num_inference_steps, sigma_shift, denoising_strength, progress_bar_cmd,
@@ -581,6 +612,47 @@ class WanVideoPipeline:
         if self.text_encoder is None or self.prompter is None:
             raise NotImplementedError("T5 text encoder not loaded: pass prompt_emb=/negative_prompt_emb=")
         return self.prompter.encode_prompt(prompt, device=self.device)
+
+    def encode_input_video(self, input_video, input_latents, height, width, num_frames, tiled, tile_size,
+                           tile_stride, vace_reference_image=None):
+        """WanVideoUnit_InputVideoEmbedder (wan_video_new.py:598-609): preprocess + VAE-encode the
+        video (or take its precomputed latents), with the latent of the one reference image, encoded
+        untiled, in front along time -> (1, 16, f + T', h, w) bf16.  The reference neither truncates
+        nor resizes the video here, so a video that does not match the call is an error."""
+        from .vae import frames_to_u8, preprocess_video
+        t_lat = (num_frames - 1) // 4 + 1
+        want = (1, 16, t_lat, height // 8, width // 8)
+        refs = None
+        if vace_reference_image is not None:
+            refs = vace_reference_image              # a list of images, (f, H, W, 3) uint8, or one image
+            if not (isinstance(refs, (list, tuple)) or (isinstance(refs, torch.Tensor) and refs.dim() == 4)):
+                refs = [refs]
+            if len(refs) != 1:
+                # :609 concatenates f reference latents as a batch of f onto the batch-1 video latents
+                raise ValueError(f"input_video takes exactly one vace_reference_image (got {len(refs)}): the "
+                                 "reference pipeline's latent shapes only agree for one")
+        if input_video is not None:
+            frames = frames_to_u8(input_video, self.device)
+            if frames.shape[0] != num_frames:
+                raise ValueError(f"input_video has {frames.shape[0]} frames, the call asks for num_frames={num_frames}")
+            if tuple(frames.shape[1:3]) != (height, width):
+                raise ValueError(f"input_video frames are {frames.shape[1]}x{frames.shape[2]}, the call asks for "
+                                 f"{height}x{width}")
+        elif tuple(input_latents.shape) != want:
+            raise ValueError(f"input_latents must be {want}, got {tuple(input_latents.shape)}")
+        if self.vae is None and (input_video is not None or refs is not None):
+            raise RuntimeError("input_video encoding requires a loaded Wan2.1 VAE (or pass input_latents=)")
+        if input_video is not None:
+            input_latents = self.vae.encode(preprocess_video(frames), self.device, tiled=tiled, tile_size=tile_size,
+                                            tile_stride=tile_stride)
+        input_latents = input_latents.to(device=self.device, dtype=self.torch_dtype)
+        if refs is not None:
+            r = frames_to_u8(refs, self.device)
+            if tuple(r.shape[1:3]) != (height, width):
+                raise ValueError(f"vace_reference_image must be {height}x{width}, got {r.shape[1]}x{r.shape[2]}")
+            ref_latents = self.vae.encode(preprocess_video(r), self.device)             # :608 (untiled)
+            input_latents = torch.cat([ref_latents.to(self.torch_dtype), input_latents], dim=2)
+        return input_latents.contiguous()
 
     def encode_vace(self, vace_video, vace_video_mask, height, width, num_frames, tiled, tile_size, tile_stride,
                     vace_reference_image=None):

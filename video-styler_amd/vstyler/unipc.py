@@ -159,6 +159,23 @@ class FlowUniPCMultistepScheduler:
         self._step_index += 1
         return (prev,)
 
+    def add_noise(self, original_samples, noise, timesteps):
+        """fm_solvers_unipc.py:760-800 with begin_index None: sigma from index_for_timestep,
+        (1 - sigma) * x0 + sigma * noise op by op in fp32 (vs_flow_add_noise).  One timestep (the
+        enhancer's use, text2video.py:362-368); the multistep state is not touched."""
+        if original_samples.dtype != torch.float32 or noise.dtype != torch.float32:
+            raise ValueError("UniPC state is fp32: pass fp32 original_samples / noise")
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps first")
+        t = timesteps.cpu() if isinstance(timesteps, torch.Tensor) else timesteps
+        if isinstance(t, torch.Tensor):
+            if t.numel() != 1:
+                raise NotImplementedError("add_noise: one timestep for the whole batch")
+            t = t.reshape(())
+        from . import kernels as K
+        sigma = self.sigmas[self.index_for_timestep(t)]
+        return K.flow_add_noise(original_samples.contiguous(), noise.contiguous(), float(sigma))
+
 
 def cast(src, dst):
     """fp32 <-> bf16 elementwise (vs_cast)."""

@@ -513,6 +513,20 @@ def frames_to_u8(frames, device):
     return t.to(device).contiguous()
 
 
+def preprocess_video(frames_u8):
+    """BasePipeline.preprocess_video (utils/__init__.py:60-73) of (T, H, W, 3) uint8 device frames
+    -> (1, 3, T, H, W) bf16 in [-1, 1]: the reactive output of vs_vace_prepare with mask ones
+    (v*1 + 0*0 is exact in bf16)."""
+    T, H, W = frames_u8.shape[:3]
+    dev = frames_u8.device
+    pre = torch.empty((1, 3, T, H, W), dtype=BF16, device=dev)
+    tmp = torch.empty_like(pre)
+    m = torch.empty((T, H, W), dtype=BF16, device=dev)
+    _lib.check(_lib.load().vs_vace_prepare(frames_u8.data_ptr(), None, tmp.data_ptr(), pre.data_ptr(), m.data_ptr(),
+                                           T, H, W, _stream(frames_u8)))
+    return pre
+
+
 def vace_context(vae, vace_video=None, vace_video_mask=None, num_frames=None, height=None, width=None,
                  tiled=True, tile_size=(30, 52), tile_stride=(15, 26), vace_reference_image=None):
     """WanVideoUnit_VACE.process (wan_video_new.py:861-920)
@@ -548,13 +562,7 @@ def vace_context(vae, vace_video=None, vace_video_mask=None, num_frames=None, he
         nref = r.shape[0]
         if r.shape[1:3] != (H, W):
             raise ValueError(f"vace_reference_image must be {H}x{W}, got {tuple(r.shape[1:3])}")
-        # preprocess_video of the references = the reactive output of vs_vace_prepare with mask ones
-        # (v*1 + 0*0 is exact in bf16)
-        r_pre = torch.empty((1, 3, nref, H, W), dtype=BF16, device=dev)
-        r_tmp = torch.empty_like(r_pre)
-        r_m = torch.empty((nref, H, W), dtype=BF16, device=dev)
-        _lib.check(lib.vs_vace_prepare(r.data_ptr(), None, r_tmp.data_ptr(), r_pre.data_ptr(), r_m.data_ptr(),
-                                       nref, H, W, st))
+        r_pre = preprocess_video(r)
     out = torch.empty((1, 96, nref + t_lat, H // 8, W // 8), dtype=BF16, device=dev)
     if nref:
         rl = vae.encode([r_pre[0, :, j:j + 1] for j in range(nref)], dev, tiled=tiled, tile_size=tile_size,

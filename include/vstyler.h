@@ -445,6 +445,26 @@ int vs_cast(const void* src, void* dst, long long n, int to_bf16, void* stream);
 int vs_vae_copy_frames(const void* src, long long src_ns, void* dst, long long dst_ns, int n,
                        long long frame_elems, void* stream);
 
+/* Temporal sliding window over the DiT step (TemporalTiler_BCTHW.run,
+ * diffsynth/pipelines/wan_video_new.py:1207-1256), in the reference's bf16 arithmetic: one rounding
+ * per tensor op, every op one fp32 operation rounded to nearest-even bf16, no contraction.
+ *
+ * vs_window_blend accumulates one window's model output out[bc][l][plane] into value[bc][t][plane] at
+ * frame offset t0 (:1252): value[b][t0+j][p] = bf16(value[b][t0+j][p] + bf16(out[b][j][p] * mask[j])),
+ * mask a bf16 vector of l elements built by the host (vstyler.window).  value starts at +0.0, so an
+ * exact zero keeps the reference's sign (0 + (-0) = +0).  out is only read.
+ * vs_window_finish divides by the accumulated bf16 weight[t] (:1254), which depends on (t, size,
+ * stride) only and comes from the host: out[b][f][p] = bf16(value[b][f][p] / weight[f]); out may be
+ * value.
+ * All tensors bf16 and contiguous; plane = H*W of a latent frame, any positive value (16-byte
+ * accesses wherever the addresses allow, element accesses for the rest).  VS_E_INVALID: a null
+ * pointer, a non-positive size, t0 < 0 or t0 + l > t, out / value not 16-byte aligned, mask / weight
+ * not 2-byte aligned.  No allocation; runs on `stream` (capturable). */
+int vs_window_blend(const void* out, const void* mask, void* value, int bc, int t, int l, int t0,
+                    long long plane, void* stream);
+int vs_window_finish(const void* value, const void* weight, void* out, int bc, int t, long long plane,
+                     void* stream);
+
 
 #ifdef __cplusplus
 }

@@ -811,3 +811,120 @@ extern "C" int vs_cast(const void* src, void* dst, long long n, int to_bf16, voi
     VS_CHECK_LAUNCH();
     return VS_OK;
 }
+
+// ---- temporal sliding window (TemporalTiler_BCTHW, diffsynth/pipelines/wan_video_new.py:1207-1256) ----
+namespace {
+
+// value[bc][t0+j][p] = bf16(value + bf16(out[bc][j][p] * mask[j])) (:1252).  Row bc of the window is
+// L*plane contiguous elements on both sides, but its base in `value`, (bc*T + t0)*plane, and in `out`,
+// bc*L*plane, need not be a multiple of 8 elements (plane 60), and the two differ: each row is cut
+// into a scalar head up to value's first 16-byte boundary (chunk 0), 8-element chunks with 16-byte
+// accesses to value (out too where its address allows, element loads otherwise) and a scalar tail.
+__global__ __launch_bounds__(256) void window_blend_kernel(const bf16_t* __restrict__ out,
+                                                           const bf16_t* __restrict__ mask,
+                                                           bf16_t* __restrict__ value, int T, int L, int t0,
+                                                           long long plane, long long cpr, long long total) {
+    const long long i = blockIdx.x * 256LL + threadIdx.x;
+    if (i >= total) return;
+    const long long bc = i / cpr, c = i - bc * cpr;
+    const long long n = L * plane;
+    const long long voff = (bc * T + t0) * plane, ooff = bc * n;
+    const long long head = (8 - (voff & 7)) & 7;
+    long long lo, hi;
+    if (c == 0) {
+        lo = 0;
+        hi = head < n ? head : n;
+    } else {
+        lo = head + (c - 1) * 8;
+        hi = lo + 8 < n ? lo + 8 : n;
+    }
+    if (lo >= hi) return;
+    long long j = lo / plane, r = lo - j * plane;       // frame of element lo, offset in its plane
+    bf16_t* v = value + voff;
+    const bf16_t* o = out + ooff;
+    if (c > 0 && hi - lo == 8) {
+        float vv[8], ov[8];
+        unpack8(*reinterpret_cast<const u32x4_t*>(v + lo), vv);
+        if (((ooff + lo) & 7) == 0) {
+            unpack8(*reinterpret_cast<const u32x4_t*>(o + lo), ov);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ov[e] = bf2f(o[lo + e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            vv[e] = vv[e] + rbf(ov[e] * bf2f(mask[j]));
+            if (++r == plane) {
+                r = 0;
+                ++j;
+            }
+        }
+        *reinterpret_cast<u32x4_t*>(v + lo) = pack8(vv);
+        return;
+    }
+    for (long long e = lo; e < hi; ++e) {
+        v[e] = (bf16_t)f2bf(bf2f(v[e]) + rbf(bf2f(o[e]) * bf2f(mask[j])));
+        if (++r == plane) {
+            r = 0;
+            ++j;
+        }
+    }
+}
+
+// out[bc][t][p] = bf16(value[bc][t][p] / weight[t]) (:1254), an IEEE fp32 division.  No __restrict__
+// on value / out: they may be the same tensor (each thread reads its elements before it writes them).
+__global__ __launch_bounds__(256) void window_finish_kernel(const bf16_t* value, const bf16_t* __restrict__ weight,
+                                                            bf16_t* out, int T, long long plane, long long n) {
+    const long long lo = (blockIdx.x * 256LL + threadIdx.x) * 8;
+    if (lo >= n) return;
+    const long long f = lo / plane;
+    long long r = lo - f * plane;
+    int t = (int)(f % T);
+    if (lo + 8 <= n) {
+        float vv[8];
+        unpack8(*reinterpret_cast<const u32x4_t*>(value + lo), vv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            vv[e] = vv[e] / bf2f(weight[t]);
+            if (++r == plane) {
+                r = 0;
+                if (++t == T) t = 0;
+            }
+        }
+        *reinterpret_cast<u32x4_t*>(out + lo) = pack8(vv);
+        return;
+    }
+    for (long long e = lo; e < n; ++e) {
+        out[e] = (bf16_t)f2bf(bf2f(value[e]) / bf2f(weight[t]));
+        if (++r == plane) {
+            r = 0;
+            if (++t == T) t = 0;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int vs_window_blend(const void* out, const void* mask, void* value, int bc, int t, int l, int t0,
+                               long long plane, void* stream) {
+    if (!out || !mask || !value || bc <= 0 || t <= 0 || l <= 0 || t0 < 0 || plane <= 0) return VS_E_INVALID;
+    if ((long long)t0 + l > t) return VS_E_INVALID;
+    if (!al16(out) || !al16(value) || (reinterpret_cast<uintptr_t>(mask) & 1)) return VS_E_INVALID;
+    const long long cpr = 1 + (l * plane + 7) / 8;      // head chunk + 8-element chunks (the last: the tail)
+    const long long total = bc * cpr;
+    hipLaunchKernelGGL(window_blend_kernel, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)out, (const bf16_t*)mask, (bf16_t*)value, t, l, t0, plane, cpr, total);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+
+extern "C" int vs_window_finish(const void* value, const void* weight, void* out, int bc, int t, long long plane,
+                                void* stream) {
+    if (!value || !weight || !out || bc <= 0 || t <= 0 || plane <= 0) return VS_E_INVALID;
+    if (!al16(value) || !al16(out) || (reinterpret_cast<uintptr_t>(weight) & 1)) return VS_E_INVALID;
+    const long long n = (long long)bc * t * plane;
+    hipLaunchKernelGGL(window_finish_kernel, dim3(nblk((n + 7) / 8, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)value, (const bf16_t*)weight, (bf16_t*)out, t, plane, n);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}

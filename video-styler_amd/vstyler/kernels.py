@@ -393,6 +393,59 @@ def flow_add_noise(x0, noise, sigma, out=None):
     return out
 
 
+def _bcthw(t, name):
+    _req(t, name)
+    if t.dim() != 5 or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous [B, C, T, H, W] tensor, got {tuple(t.shape)}")
+    return t
+
+
+def _frame_vec(v, n, like, name):
+    if v.dtype != BF16 or v.device != like.device or v.dim() != 1 or v.shape[0] != n or not v.is_contiguous():
+        raise ValueError(f"{name}: expected {n} contiguous bfloat16 elements on {like.device}")
+    return v
+
+
+def window_gather(src, t0, dst):
+    """dst[B, C, L, H, W] = src[:, :, t0:t0 + L] (vs_vae_copy_frames: one strided copy, no allocation)."""
+    _bcthw(src, "src"), _bcthw(dst, "dst")
+    B, C, T, H, W = src.shape
+    L = dst.shape[2]
+    if dst.shape != (B, C, L, H, W) or t0 < 0 or t0 + L > T:
+        raise ValueError(f"window_gather: frames [{t0}, {t0 + L}) of {tuple(src.shape)} into {tuple(dst.shape)}")
+    plane = H * W
+    _lib.check(_lib.load().vs_vae_copy_frames(src.data_ptr() + 2 * t0 * plane, T * plane, dst.data_ptr(), L * plane,
+                                              B * C, L * plane, _stream(src)))
+    return dst
+
+
+def window_blend(out, mask, value, t0):
+    """value[:, :, t0:t0 + L] += out * mask in the reference's bf16 arithmetic (vs_window_blend);
+    out [B, C, L, H, W], mask [L], value [B, C, T, H, W]."""
+    _bcthw(out, "out"), _bcthw(value, "value")
+    B, C, T, H, W = value.shape
+    L = out.shape[2]
+    if out.shape != (B, C, L, H, W) or out.device != value.device:
+        raise ValueError(f"window_blend: out {tuple(out.shape)} does not match value {tuple(value.shape)}")
+    _frame_vec(mask, L, value, "mask")
+    _lib.check(_lib.load().vs_window_blend(out.data_ptr(), mask.data_ptr(), value.data_ptr(), B * C, T, L, int(t0),
+                                           H * W, _stream(value)))
+    return value
+
+
+def window_finish(value, weight, out=None):
+    """value / weight[T] in bf16 (vs_window_finish), in place by default."""
+    _bcthw(value, "value")
+    out = value if out is None else _bcthw(out, "out")
+    B, C, T, H, W = value.shape
+    if out.shape != value.shape or out.device != value.device:
+        raise ValueError(f"window_finish: out {tuple(out.shape)} does not match value {tuple(value.shape)}")
+    _frame_vec(weight, T, value, "weight")
+    _lib.check(_lib.load().vs_window_finish(value.data_ptr(), weight.data_ptr(), out.data_ptr(), B * C, T, H * W,
+                                            _stream(value)))
+    return out
+
+
 def time_sinusoid(t, out):
     _lib.check(_lib.load().vs_time_sinusoid(t.data_ptr(), out.data_ptr(), t.numel(), out.shape[-1], _stream(t)))
     return out
@@ -422,5 +475,6 @@ def ulysses_permute(src, dst, batch, s_local, world, cols_per_rank, ld_local, js
 
 
 __all__ = ["set_option", "get_option", "options", "ulysses_permute", "gemm", "attention", "layernorm_modulate", "rmsnorm_rope", "patchify", "unpatchify", "cfg_euler", "flow_add_noise",
+           "window_gather", "window_blend", "window_finish",
            "time_sinusoid", "mod_add", "axpy", "VS_EPI_BIAS", "VS_EPI_GELU", "VS_EPI_SILU", "VS_EPI_GATE_RES",
            "VS_EPI_RES"]

@@ -245,20 +245,23 @@ class Sequential3(nn.Module):
 
 
 class Workspace:
-    """Scratch buffers reused across blocks/steps (allocated once per shape; kernels never allocate)."""
+    """Scratch buffers reused across blocks/steps (kernels never allocate).  A buffer is keyed by
+    (name, shape, dtype) and lives as long as the workspace: forwards of different sizes that alternate
+    -- the full and the ragged window of a sliding-window step -- each keep their own set, so after one
+    forward at every size nothing is allocated and no buffer moves (a captured step stays valid)."""
 
     def __init__(self, device):
         self.device = device
         self.bufs = {}
 
     def get(self, name, shape, dtype=BF16):
-        shape = tuple(int(s) for s in shape)
-        t = self.bufs.get(name)
-        if t is None or t.shape != shape or t.dtype != dtype:
-            t = torch.empty(shape, device=self.device, dtype=dtype)
+        key = (name, tuple(int(s) for s in shape), dtype)
+        t = self.bufs.get(key)
+        if t is None:
+            t = torch.empty(key[1], device=self.device, dtype=dtype)
             if host_option("ws_poison"):    # debugging aid: NaN-fill so a read-before-write shows up
                 t.view(torch.uint8).fill_(0xFF)
-            self.bufs[name] = t
+            self.bufs[key] = t
         return t
 
 

@@ -17,6 +17,7 @@ from . import kernels as K
 from .flow_match import FlowMatchScheduler
 from .models import RunCtx, Workspace, WanModel, VaceWanModel
 from .options import host_option
+from .window import check_window_args, plan_windows
 
 BF16 = torch.bfloat16
 
@@ -31,14 +32,65 @@ def _workspace(device):
 
 
 _UNSUPPORTED = ("clip_feature", "y", "reference_latents", "audio_embeds", "motion_latents", "s2v_pose_latents",
-                "motion_bucket_id", "pose_latents", "face_pixel_values", "control_camera_latents_input",
-                "sliding_window_size")
+                "motion_bucket_id", "pose_latents", "face_pixel_values", "control_camera_latents_input")
+
+_WINDOW_PLANS = {}
+
+
+def _device_plan(device, T, size, stride):
+    """The host plan of (T, size, stride) with its masks and weight on `device`, built once."""
+    key = (str(torch.device(device)), T, size, stride)
+    if key not in _WINDOW_PLANS:
+        plan = plan_windows(T, size, stride)
+        _WINDOW_PLANS[key] = (plan, [m.to(device) for m in plan.masks], plan.weight.to(device))
+    return _WINDOW_PLANS[key]
+
+
+def slice_windows(x, plan):
+    """x[:, :, t:t_] of every window of the plan as contiguous bf16 tensors: what a caller that runs
+    many steps on one vace_context hands to model_fn_wan_video(vace_context_windows=)."""
+    x = x.to(BF16).contiguous()
+    B, C, T, H, W = x.shape
+    return [K.window_gather(x, t, torch.empty((B, C, t_ - t, H, W), device=x.device, dtype=BF16))
+            for t, t_ in plan.windows]
+
+
+def _windowed_forward(size, stride, dit, motion_controller, vace, animate_adapter, latents, vace_context,
+                      vace_context_windows, **fwd):
+    """TemporalTiler_BCTHW.run (wan_video_new.py:1229-1256) around the plain forward: every window
+    [t, t_) of the latent time axis is an ordinary forward of latents[:, :, t:t_] (RoPE positions
+    0..t_-t-1, same timestep and context), blended into `value` with the window's mask and divided by
+    the accumulated weight at the end, in the reference's bf16 arithmetic (vs_window_blend /
+    vs_window_finish).  Unlike the reference, whose tiler slices only latents and y, vace_context is
+    cut with the same [t, t_): a full-length context does not match the window's tokens."""
+    device = latents.device
+    ws = _workspace(device)
+    lat = latents.to(BF16).contiguous()
+    Bl, C, T, H, W = lat.shape
+    plan, masks, weight = _device_plan(device, T, size, stride)
+    use_vace = vace_context is not None and vace is not None
+    if use_vace and vace_context_windows is None:
+        vc = vace_context.to(BF16).contiguous()
+    value = None
+    for i, (t, t_) in enumerate(plan.windows):
+        lw = K.window_gather(lat, t, ws.get("win_lat", (Bl, C, t_ - t, H, W)))
+        vw = None
+        if use_vace and vace_context_windows is not None:
+            vw = vace_context_windows[i]
+        elif use_vace:
+            vw = K.window_gather(vc, t, ws.get("win_vace", (vc.shape[0], vc.shape[1], t_ - t, H, W)))
+        out = model_fn_wan_video(dit, motion_controller, vace, animate_adapter, latents=lw, vace_context=vw, **fwd)
+        if value is None:
+            value = torch.zeros((out.shape[0], out.shape[1], T, H, W), device=device, dtype=BF16)
+        K.window_blend(out, masks[i], value, t)
+    return K.window_finish(value, weight)
 
 
 def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel = None, animate_adapter=None,
                        latents: torch.Tensor = None, timestep: torch.Tensor = None, context: torch.Tensor = None,
                        vace_context=None, vace_scale=1.0, use_unified_sequence_parallel: bool = False,
-                       sp_group=None, slg_blocks=(), tea_cache=None, cfg_sample=0, **kwargs):
+                       sp_group=None, slg_blocks=(), tea_cache=None, cfg_sample=0, sliding_window_size=None,
+                       sliding_window_stride=None, vace_context_windows=None, **kwargs):
     """One DiT(+VACE) forward (wan_video_new.py:1338-1468) -> [B,16,T,H,W] bf16 velocity.
 
     slg_blocks: skip-layer guidance (config 5, ComfyUI WanVideoSLG): the listed main blocks are
@@ -51,10 +103,25 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
 
     sp_group may be a vstyler.usp.CfgParallel: a batch-2 (CFG) forward then runs as this rank's
     sample only (batch 1, Ulysses over its half of the ranks) and the two samples' outputs are
-    all-gathered across the halves -- the same [2,16,T,H,W] as the batched forward."""
+    all-gathered across the halves -- the same [2,16,T,H,W] as the batched forward.
+
+    sliding_window_size / sliding_window_stride (latent frames, both ints, 1 <= stride <= size): the
+    temporal sliding window of wan_video_new.py:1291-1315 (_windowed_forward).  stride alone is
+    ignored, as in the reference.  One window (size >= T) takes the plain path.  vace_context_windows:
+    the vace_context already cut per window (slice_windows), so a denoising loop gathers it once."""
     for name in _UNSUPPORTED:
         if kwargs.get(name) is not None:
             raise NotImplementedError(f"model_fn_wan_video: '{name}' is outside the Ditto hot path")
+    win = check_window_args(sliding_window_size, sliding_window_stride)
+    if win is not None and len(plan_windows(latents.shape[2], *win).windows) > 1:
+        if tea_cache is not None:
+            # the reference hands one TeaCache state to every window (:1304), which compares and reuses
+            # residuals across different windows
+            raise NotImplementedError("model_fn_wan_video: tea_cache with a temporal sliding window")
+        return _windowed_forward(win[0], win[1], dit, motion_controller, vace, animate_adapter, latents, vace_context,
+                                 vace_context_windows, timestep=timestep, context=context, vace_scale=vace_scale,
+                                 use_unified_sequence_parallel=use_unified_sequence_parallel, sp_group=sp_group,
+                                 slg_blocks=slg_blocks, cfg_sample=cfg_sample, **kwargs)
     if use_unified_sequence_parallel:
         from .usp import CfgParallel, get_default_group
         plan = sp_group if sp_group is not None else get_default_group()
@@ -446,7 +513,7 @@ class WanVideoPipeline:
     # ---------------------------------------------------------------- denoise
     def denoise(self, latents, context_posi, context_nega, vace_context=None, vace_scale=1.0, cfg_scale=5.0,
                 num_inference_steps=50, sigma_shift=5.0, denoising_strength=1.0, progress_bar_cmd=None,
-                use_graph=None, tea_cache=None):
+                use_graph=None, tea_cache=None, sliding_window_size=None, sliding_window_stride=None):
         """The loop of wan_video_new.py:515-542 (cfg_merge batched), returns the final latents.
 
         Step 0 runs eagerly (it also sizes the Workspace); the whole step -- model_fn (DiT + VACE,
@@ -455,7 +522,12 @@ class WanVideoPipeline:
         graph reads the step's bf16 timestep and fp32 dsigma from two device slots refreshed before
         each replay, so one capture serves all steps.  Under Ulysses SP the RCCL collectives (async
         all-to-alls on RCCL's stream, event-ordered) are captured with the step only with host option
-        sp_graph=1 (sp_graph_ok); eager with use_graph=False / host option graph=0."""
+        sp_graph=1 (sp_graph_ok); eager with use_graph=False / host option graph=0.
+
+        sliding_window_size / sliding_window_stride go to model_fn inside the step, so one capture
+        holds all windows of a step; the vace_context is cut per window once, here."""
+        window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context,
+                                        tea_cache)
         self.scheduler.set_timesteps(num_inference_steps, denoising_strength=denoising_strength, shift=sigma_shift)
         n_steps = len(self.scheduler.timesteps)
         use_cfg = cfg_scale != 1.0
@@ -474,7 +546,7 @@ class WanVideoPipeline:
             v = self.model_fn(dit=self.dit, vace=self.vace, latents=latents, timestep=t_buf, context=ctx,
                               vace_context=vace_context, vace_scale=vace_scale,
                               use_unified_sequence_parallel=self.use_unified_sequence_parallel,
-                              sp_group=self.sp_group, tea_cache=tea_cache)
+                              sp_group=self.sp_group, tea_cache=tea_cache, **window_kw)
             K.cfg_euler_dev(v[0:1], v[1:2] if use_cfg else None, latents, cfg_scale, d_buf)
 
         comms, plan = (), None
@@ -491,9 +563,24 @@ class WanVideoPipeline:
         self.last_graph = stepper.graph
         return latents
 
+    def _window_kwargs(self, T, size, stride, vace_context, tea_cache=None):
+        """model_fn's sliding-window arguments for a loop over T latent frames ({} without windows)."""
+        win = check_window_args(size, stride)
+        if win is None:
+            return {}
+        kw = dict(sliding_window_size=win[0], sliding_window_stride=win[1])
+        plan = plan_windows(T, *win)
+        if len(plan.windows) > 1:
+            if tea_cache is not None:
+                raise NotImplementedError("tea_cache_l1_thresh with a temporal sliding window is not supported")
+            if vace_context is not None and self.vace is not None:
+                kw["vace_context_windows"] = slice_windows(vace_context.to(self.device), plan)
+        return kw
+
     def denoise_unipc(self, latents, context_posi, context_nega, vace_context=None, vace_scale=1.0,
                       cfg_scale=1.2, num_inference_steps=4, sigma_shift=2.0, slg_blocks=(), slg_range=(0.2, 0.7),
-                      progress_bar_cmd=None, input_latents=None, forward_step=None, skip_backward_step=None):
+                      progress_bar_cmd=None, input_latents=None, forward_step=None, skip_backward_step=None,
+                      sliding_window_size=None, sliding_window_stride=None):
         """Config 5's sampler (ditto_comfyui_workflow.json WanVideoSampler 4 / 1.2 / 2.0 / unipc with
         WanVideoSLG): FlowUniPCMultistepScheduler (vstyler.unipc) on fp32 latents, CFG as one
         batch-2 forward, skip-layer guidance on the uncond sample for step fractions in slg_range.
@@ -503,7 +590,10 @@ class WanVideoPipeline:
         text2video.py:347-375): `latents` is then the noise, the loop starts from
         add_noise(input_latents, noise, timesteps[-forward_step]) and runs timesteps[-skip_backward_step:]
         (both counted from the schedule's end, in [1, n]); a step's SLG fraction stays its index in the
-        full schedule over n."""
+        full schedule over n.
+
+        sliding_window_size / sliding_window_stride: as in denoise."""
+        window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context)
         from .unipc import FlowUniPCMultistepScheduler, cast
         sched = FlowUniPCMultistepScheduler(shift=1.0)
         sched.set_timesteps(num_inference_steps, shift=sigma_shift)
@@ -537,7 +627,7 @@ class WanVideoPipeline:
             v = self.model_fn(dit=self.dit, vace=self.vace, latents=lat16, timestep=t.reshape(1).to(
                 dtype=BF16, device=self.device), context=ctx, vace_context=vace_context, vace_scale=vace_scale,
                 use_unified_sequence_parallel=self.use_unified_sequence_parallel, sp_group=self.sp_group,
-                slg_blocks=slg)
+                slg_blocks=slg, **window_kw)
             v16.zero_()
             K.cfg_euler(v[0:1], v[1:2] if use_cfg else None, v16, cfg_scale, 1.0)   # v16 = cfg combine
             cast(v16, v32)
@@ -560,11 +650,12 @@ class WanVideoPipeline:
         denoising_strength < 1 starts the loop from the video's latents re-noised to the first sigma
         of the shortened schedule (WanVideoUnit_InputVideoEmbedder, :591-614)."""
         for name, val in (("input_image", input_image), ("end_image", end_image),
-                          ("motion_bucket_id", motion_bucket_id), ("sliding_window_size", sliding_window_size)):
+                          ("motion_bucket_id", motion_bucket_id)):
             if val is not None:
                 raise NotImplementedError(f"{name} is outside the Ditto hot path of this build")
         if input_video is not None and input_latents is not None:
             raise ValueError("pass input_video or its precomputed input_latents, not both")
+        check_window_args(sliding_window_size, sliding_window_stride)
         height, width, num_frames = self.check_resize_height_width(height, width, num_frames)
         T = (num_frames - 1) // 4 + 1
         # WanVideoUnit_NoiseInitializer (wan_video_new.py:578-587): f reference images add f latent
@@ -597,7 +688,8 @@ class WanVideoPipeline:
                                negative_prompt_emb.to(self.device),
                                None if vace_context is None else vace_context.to(self.device), vace_scale,
                                cfg_scale, num_inference_steps, sigma_shift, denoising_strength, progress_bar_cmd,
-                               tea_cache=tea_cache)
+                               tea_cache=tea_cache, sliding_window_size=sliding_window_size,
+                               sliding_window_stride=sliding_window_stride)
         self.last_tea_cache = tea_cache
         if nref:                                            # :545-550
             latents = latents[:, :, nref:].contiguous()

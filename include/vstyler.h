@@ -488,6 +488,16 @@ int vs_window_blend(const void* out, const void* mask, void* value, int bc, int 
 int vs_window_finish(const void* value, const void* weight, void* out, int bc, int t, long long plane,
                      void* stream);
 
+/* Nearest-neighbour resize of uint8 channels-last frames, src [t][h][w][3] -> dst [t][h_out][w_out][3]:
+ * the enhancer's read_video (denoising_enhancing/video_enhancing_batch.py:76-77, F.interpolate's
+ * default mode on the frames; a nearest resize moves bytes, so uint8 in and out is exact).  Source
+ * index per axis as torch computes it: min((int)floorf(d * (float(in) / float(out))), in - 1), in
+ * fp32.  Both tensors contiguous, any alignment (16-byte stores from dst's first 16-byte boundary on,
+ * element stores for the head before it and the tail; w_out * 3 need not be a multiple of 16); src is
+ * only read and must not overlap dst.  VS_E_INVALID: a null pointer, a non-positive size,
+ * channels != 3.  No allocation; runs on `stream` (capturable). */
+int vs_resize_nearest_u8(const void* src, void* dst, int t, int h, int w, int h_out, int w_out, int channels,
+                         void* stream);
 
 #ifdef __cplusplus
 }

@@ -928,3 +928,80 @@ extern "C" int vs_window_finish(const void* value, const void* weight, void* out
     VS_CHECK_LAUNCH();
     return VS_OK;
 }
+
+// ---- nearest-neighbour frame resize (read_video, denoising_enhancing/video_enhancing_batch.py:76-77) ----
+namespace {
+
+// dst[t][y][x][c] = src[t][sy(y)][sx(x)][c], uint8 channels-last, with torch's nearest source index
+// s(d) = min((int)floorf(d * scale), in - 1), scale = float(in) / float(out) (one fp32 division on the
+// host, one fp32 multiply here).  The destination is walked as one flat byte array (a row is 3*Wo
+// bytes, any count): chunk 0 is the element head up to dst's first 16-byte boundary, every later
+// chunk 16 bytes gathered into one 16-byte store, the last one an element tail when it is short.
+__global__ __launch_bounds__(256) void resize_nearest_u8_kernel(const uint8_t* __restrict__ src,
+                                                                uint8_t* __restrict__ dst, int H, int W, int Ho,
+                                                                int Wo, float sh, float sw, long long head,
+                                                                long long n, long long total) {
+    const long long i = blockIdx.x * 256LL + threadIdx.x;
+    if (i >= total) return;
+    long long lo, hi;
+    if (i == 0) {
+        lo = 0;
+        hi = head < n ? head : n;
+    } else {
+        lo = head + (i - 1) * 16;
+        hi = lo + 16 < n ? lo + 16 : n;
+    }
+    if (lo >= hi) return;
+    const int cnt = (int)(hi - lo);
+    const long long px = lo / 3, row = px / Wo;
+    int c = (int)(lo - px * 3), x = (int)(px - row * Wo);
+    long long t = row / Ho;
+    int y = (int)(row - t * Ho);
+    int sy = min((int)floorf((float)y * sh), H - 1), sx = min((int)floorf((float)x * sw), W - 1);
+    const uint8_t* sr = src + (t * H + sy) * (long long)W * 3;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    const bool vec = i > 0 && cnt == 16;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        if (e < cnt) {
+            const uint32_t b = sr[sx * 3 + c];
+            if (vec)
+                w[e >> 2] |= b << (8 * (e & 3));
+            else
+                dst[lo + e] = (uint8_t)b;
+            if (e + 1 < cnt && ++c == 3) {
+                c = 0;
+                if (++x == Wo) {
+                    x = 0;
+                    if (++y == Ho) {
+                        y = 0;
+                        ++t;
+                    }
+                    sy = min((int)floorf((float)y * sh), H - 1);
+                    sr = src + (t * H + sy) * (long long)W * 3;
+                }
+                sx = min((int)floorf((float)x * sw), W - 1);
+            }
+        }
+    }
+    if (vec) {
+        u32x4_t v = {w[0], w[1], w[2], w[3]};
+        *reinterpret_cast<u32x4_t*>(dst + lo) = v;
+    }
+}
+
+}  // namespace
+
+extern "C" int vs_resize_nearest_u8(const void* src, void* dst, int t, int h, int w, int h_out, int w_out,
+                                    int channels, void* stream) {
+    if (!src || !dst || t <= 0 || h <= 0 || w <= 0 || h_out <= 0 || w_out <= 0 || channels != 3) return VS_E_INVALID;
+    const long long n = (long long)t * h_out * w_out * 3;
+    const long long head = (16 - (long long)(reinterpret_cast<uintptr_t>(dst) & 15)) & 15;
+    const long long total = 1 + (n + 15) / 16;      // the head chunk + 16-byte chunks (covers any head)
+    if ((total + 255) / 256 > 0x7fffffffLL) return VS_E_INVALID;
+    hipLaunchKernelGGL(resize_nearest_u8_kernel, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint8_t*)src, (uint8_t*)dst, h, w, h_out, w_out, (float)h / (float)h_out,
+                       (float)w / (float)w_out, head, n, total);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}

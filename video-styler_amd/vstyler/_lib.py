@@ -109,6 +109,7 @@ SIGNATURES = {
     "vs_vae_copy_frames": [_P, _LL, _P, _LL, _I, _LL, _P],
     "vs_window_blend": [_P, _P, _P, _I, _I, _I, _I, _LL, _P],
     "vs_window_finish": [_P, _P, _P, _I, _I, _LL, _P],
+    "vs_resize_nearest_u8": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "vs_sp_unique_id": [_P],
     "vs_sp_init": [_I, _I, _P, _I, ctypes.POINTER(_P)],
     "vs_sp_all_to_all": [_P, _P, _P, _LL, _P],

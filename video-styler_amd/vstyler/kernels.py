@@ -475,6 +475,25 @@ def window_finish(value, weight, out=None):
     return out
 
 
+def resize_nearest_u8(frames, height, width, out=None):
+    """(T, H, W, 3) uint8 device frames -> (T, height, width, 3) uint8, nearest neighbour with
+    F.interpolate(mode="nearest")'s source index (vs_resize_nearest_u8).  out: a contiguous uint8
+    tensor of that shape (any alignment), allocated when None."""
+    if frames.dtype != torch.uint8 or not frames.is_cuda or frames.dim() != 4 or not frames.is_contiguous():
+        raise ValueError(f"frames must be a contiguous (T, H, W, 3) uint8 device tensor, got "
+                         f"{tuple(frames.shape)} {frames.dtype}")
+    T, H, W, C = frames.shape
+    if out is None:
+        out = torch.empty((T, int(height), int(width), C), dtype=torch.uint8, device=frames.device)
+    elif out.dtype != torch.uint8 or out.device != frames.device or not out.is_contiguous() or \
+            tuple(out.shape) != (T, int(height), int(width), C):
+        raise ValueError(f"out must be a contiguous uint8 tensor {(T, int(height), int(width), C)} on "
+                         f"{frames.device}, got {tuple(out.shape)} {out.dtype}")
+    _lib.check(_lib.load().vs_resize_nearest_u8(frames.data_ptr(), out.data_ptr(), T, H, W, int(height), int(width),
+                                                C, _stream(frames)))
+    return out
+
+
 def time_sinusoid(t, out):
     _lib.check(_lib.load().vs_time_sinusoid(t.data_ptr(), out.data_ptr(), t.numel(), out.shape[-1], _stream(t)))
     return out

@@ -271,16 +271,33 @@ def build_text_encoder(state_dict, device):
     return WanTextEncoder(device=device, **cfg).load_state_dict(state_dict)
 
 
+def _check_experts(dits):
+    """The two experts of one pipeline share the Workspace and every launch shape."""
+    if len(dits) == 2:
+        for name in ("dim", "num_heads", "num_layers"):
+            a, b = (len(d.blocks) if name == "num_layers" else getattr(d, name) for d in dits)
+            if a != b:
+                raise ValueError(f"the two DiT experts differ in {name}: {a} vs {b}")
+
+
 def load_models(paths, device="cuda", fp8_weights="fold"):
     """Returns {'wan_video_dit': WanModel, 'wan_video_vace': VaceWanModel, ...} for the files given.
     fp8_weights: "fold" -- e4m3 tensors become bf16 weights (upcast times scale_weight: normalize_keys)
     and nothing else; "keep" -- the same bf16 model (LoRA merge, hot-load and the bf16 layers work
     unchanged), whose block Linears additionally run the file's e4m3 bytes and scales on the fp8 GEMMs
     (attach_fp8_weights) instead of a second quantisation by quantize_fp8_.  A file without e4m3
-    tensors loads the same either way."""
+    tensors loads the same either way.
+
+    Two experts (the Wan2.2 A14B high-noise / low-noise pair): DiTs and VACE modules are collected in
+    file order, 'wan_video_dit' / 'wan_video_vace' the first and 'wan_video_dit2' / 'wan_video_vace2'
+    the second of each (the reference's fetch_model(..., index=2), wan_video_new.py:381-391).  A
+    combined DiT+VACE file gives one of each; VACE-module-only files pair with the DiTs in order.  A
+    third DiT or VACE module, or experts whose dim, num_heads or num_layers differ, is a ValueError.
+    fp8_weights="keep" attaches every file's tensors to the models built from that file."""
     if fp8_weights not in ("fold", "keep"):
         raise ValueError(f"fp8_weights must be 'fold' or 'keep', got {fp8_weights!r}")
     out = {}
+    dits, vaces = [], []
     vace_only = []
     for path in paths:
         raw = load_state_dict(path, device="cpu")
@@ -296,24 +313,36 @@ def load_models(paths, device="cuda", fp8_weights="fold"):
             continue
         if sd and all(k.startswith("vace") for k in sd):
             # a VACE-module-only file (the ComfyUI workflow's WanVideoVACEModelSelect input): built
-            # once every file is read, with the DiT's block count when a DiT came with it
+            # once every file is read, with its DiT's block count when a DiT came with it
             vace_only.append((sd, fp8))
             continue
         dit = build_dit(sd, device)
         if dit is not None:
-            out["wan_video_dit"] = dit
+            if len(dits) == 2:
+                raise ValueError(f"{path}: a third DiT checkpoint (a pipeline holds two experts, dit and dit2)")
+            dits.append(dit)
+            _check_experts(dits)
             vace = build_vace(sd, device, num_layers=len(dit.blocks))
             if vace is not None:
-                out["wan_video_vace"] = vace
+                if len(vaces) == 2:
+                    raise ValueError(f"{path}: a third VACE module (a pipeline holds vace and vace2)")
+                vaces.append(vace)
             if fp8:
                 attach_fp8_weights(dit, fp8)
                 if vace is not None:
                     attach_fp8_weights(vace, fp8)
             continue
         raise NotImplementedError(f"unrecognised checkpoint {path} (hash {hash_state_dict_keys(sd)})")
-    dit = out.get("wan_video_dit")
     for sd, fp8 in vace_only:
-        out["wan_video_vace"] = build_vace(sd, device, num_layers=len(dit.blocks) if dit is not None else None)
+        if len(vaces) == 2:
+            raise ValueError("a third VACE module (a pipeline holds vace and vace2)")
+        # the i-th VACE module pairs with the i-th DiT (one DiT: with that one)
+        dit = dits[min(len(vaces), len(dits) - 1)] if dits else None
+        vace = build_vace(sd, device, num_layers=len(dit.blocks) if dit is not None else None)
         if fp8:
-            attach_fp8_weights(out["wan_video_vace"], fp8)
+            attach_fp8_weights(vace, fp8)
+        vaces.append(vace)
+    for name, models in (("wan_video_dit", dits), ("wan_video_vace", vaces)):
+        for model, suffix in zip(models, ("", "2")):
+            out[name + suffix] = model
     return out

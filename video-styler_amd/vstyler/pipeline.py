@@ -317,14 +317,23 @@ class DenoiseStepper:
     second stream forked from it and joined back, so the collectives overlap the compute inside
     the graph while RCCL itself only ever runs on the origin stream.  plan: the step's SP plan (None
     without SP): the capture is refused while a side-stream communicator reachable from it is not
-    bound to the capture stream (usp.unbound_side_comms)."""
+    bound to the capture stream (usp.unbound_side_comms).
 
-    def __init__(self, step_fn, timesteps_bf16, dsigmas_f32, use_graph=True, on_replay=None, comms=(), plan=None):
+    A graph holds the weight pointers of the model it captured, so a loop over two experts runs one
+    stepper per expert segment (WanVideoPipeline.denoise)."""
+
+    def __init__(self, step_fn, timesteps_bf16, dsigmas_f32, use_graph=True, on_replay=None, comms=(), plan=None,
+                 stream=None):
         self.step_fn, self.ts, self.ds = step_fn, timesteps_bf16, dsigmas_f32
         self.t_buf, self.d_buf = timesteps_bf16[0:1].clone(), dsigmas_f32[0:1].clone()
         self.use_graph, self.graph, self.on_replay = use_graph, None, on_replay
         dev = self.t_buf.device
-        self.stream = torch.cuda.Stream(device=dev) if use_graph else None
+        # stream: the dedicated stream of an earlier stepper of the same loop (one per expert segment),
+        # so every segment's eager step and capture find the split-tail workspaces of the first
+        if not use_graph:
+            self.stream = None
+        else:
+            self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
         self.comms = list(comms) if use_graph else []
         self.plan = plan
         self.compute = torch.cuda.Stream(device=dev) if self.comms else None
@@ -445,6 +454,9 @@ class WanVideoPipeline:
         models = load_models(paths, device=device, fp8_weights=fp8_weights)
         pipe.dit = models.get("wan_video_dit")
         pipe.vace = models.get("wan_video_vace")
+        # the second expert of a Wan2.2 A14B pair, in file order (fetch_model(..., index=2), :381-391)
+        pipe.dit2 = models.get("wan_video_dit2")
+        pipe.vace2 = models.get("wan_video_vace2")
         pipe.vae = models.get("wan_video_vae")
         pipe.text_encoder = models.get("wan_video_text_encoder")
         if pipe.text_encoder is not None:
@@ -514,9 +526,17 @@ class WanVideoPipeline:
         return noise.to(dtype=self.torch_dtype, device=self.device)
 
     # ---------------------------------------------------------------- denoise
+    def _expert(self, e):
+        """(dit, vace) of expert 1 or 2; an expert the plan never selects is never looked at."""
+        dit, vace = (self.dit, self.vace) if e == 1 else (self.dit2, self.vace2)
+        if dit is None:
+            raise RuntimeError(f"the schedule selects expert {e}, but pipe.dit{'' if e == 1 else '2'} is not loaded")
+        return dit, vace
+
     def denoise(self, latents, context_posi, context_nega, vace_context=None, vace_scale=1.0, cfg_scale=5.0,
                 num_inference_steps=50, sigma_shift=5.0, denoising_strength=1.0, progress_bar_cmd=None,
-                use_graph=None, tea_cache=None, sliding_window_size=None, sliding_window_stride=None):
+                use_graph=None, tea_cache=None, sliding_window_size=None, sliding_window_stride=None,
+                switch_DiT_boundary=0.875):
         """The loop of wan_video_new.py:515-542 (cfg_merge batched), returns the final latents.
 
         Step 0 runs eagerly (it also sizes the Workspace); the whole step -- model_fn (DiT + VACE,
@@ -528,42 +548,74 @@ class WanVideoPipeline:
         sp_graph=1 (sp_graph_ok); eager with use_graph=False / host option graph=0.
 
         sliding_window_size / sliding_window_stride go to model_fn inside the step, so one capture
-        holds all windows of a step; the vace_context is cut per window once, here."""
+        holds all windows of a step; the vace_context is cut per window once, here.
+
+        Two experts (dit2 set; wan_video_new.py:518-523): the steps whose fp32 timestep is below
+        switch_DiT_boundary * 1000 run on dit2 / vace2 (experts.plan_experts; vace2 None: no hints,
+        as the reference's models["vace"] = self.vace2).  Every segment of the plan is the loop above
+        on its own: first step eager, then captured and replayed (a graph holds one expert's weight
+        pointers), unless it has a single step.  The segments share the Workspace, the capture stream
+        and the latents.  cfg_scale may be a (low_noise, high_noise) pair: dit takes [1], dit2 [0]; a
+        segment whose scale is exactly 1.0 runs the batch-1 forward.  last_graphs: every segment's
+        graph (None for an eager one); last_graph: the last segment's."""
+        from .experts import expert_cfg_scales, plan_experts
+        has2 = self.dit2 is not None
+        scales = expert_cfg_scales(cfg_scale, has2)
+        if has2 and tea_cache is not None:
+            # the reference hands one TeaCache state to both experts and has no coefficients for them
+            raise NotImplementedError("tea_cache_l1_thresh with a second expert (dit2) is not supported")
         window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context,
                                         tea_cache)
         self.scheduler.set_timesteps(num_inference_steps, denoising_strength=denoising_strength, shift=sigma_shift)
         n_steps = len(self.scheduler.timesteps)
-        use_cfg = cfg_scale != 1.0
+        segments = plan_experts(self.scheduler.timesteps, switch_DiT_boundary, has2)
         if use_graph is None:
             use_graph = bool(host_option("graph"))
         # TeaCache decides per step on the host (wan_video_new.py:1173-1192): eager steps
-        use_graph = use_graph and n_steps > 1 and tea_cache is None and \
+        use_graph = use_graph and tea_cache is None and \
             (not self.use_unified_sequence_parallel or sp_graph_ok(self.sp_group))
-        ctx = torch.cat([context_posi, context_nega], 0) if use_cfg else context_posi
         latents = latents.to(device=self.device, dtype=BF16).contiguous().clone()
         ts = self.scheduler.timesteps.to(dtype=BF16).to(self.device)                     # :526
         ds = torch.tensor([self.scheduler.delta(i) for i in range(n_steps)], dtype=torch.float32,
                           device=self.device)
+        ctx_cfg = None
 
-        def step(t_buf, d_buf):
-            v = self.model_fn(dit=self.dit, vace=self.vace, latents=latents, timestep=t_buf, context=ctx,
-                              vace_context=vace_context, vace_scale=vace_scale,
-                              use_unified_sequence_parallel=self.use_unified_sequence_parallel,
-                              sp_group=self.sp_group, tea_cache=tea_cache, **window_kw)
-            K.cfg_euler_dev(v[0:1], v[1:2] if use_cfg else None, latents, cfg_scale, d_buf)
+        def make_step(dit, vace, scale):
+            nonlocal ctx_cfg
+            use_cfg = scale != 1.0
+            if use_cfg and ctx_cfg is None:
+                ctx_cfg = torch.cat([context_posi, context_nega], 0)
+            ctx = ctx_cfg if use_cfg else context_posi
 
-        comms, plan = (), None
+            def step(t_buf, d_buf):
+                v = self.model_fn(dit=dit, vace=vace, latents=latents, timestep=t_buf, context=ctx,
+                                  vace_context=vace_context, vace_scale=vace_scale,
+                                  use_unified_sequence_parallel=self.use_unified_sequence_parallel,
+                                  sp_group=self.sp_group, tea_cache=tea_cache, **window_kw)
+                K.cfg_euler_dev(v[0:1], v[1:2] if use_cfg else None, latents, scale, d_buf)
+            return step
+
+        plan = None
         if self.use_unified_sequence_parallel:
             from .usp import get_default_group, plan_native_comms
             plan = self.sp_group if self.sp_group is not None else get_default_group()
-            comms = plan_native_comms(plan) if use_graph else ()
-        stepper = DenoiseStepper(step, ts, ds, use_graph, comms=comms, plan=plan)
+        steppers = []
+        stream = None
+        for first, last, e in segments:
+            dit, vace = self._expert(e)
+            seg_graph = use_graph and last > first
+            comms = plan_native_comms(plan) if plan is not None and seg_graph else ()
+            st = DenoiseStepper(make_step(dit, vace, scales[e - 1]), ts, ds, seg_graph, comms=comms, plan=plan,
+                                stream=stream)
+            stream = st.stream if st.stream is not None else stream
+            steppers += [st] * (last - first + 1)
         steps = range(n_steps)
         if progress_bar_cmd is not None:
             steps = progress_bar_cmd(steps)
         for i in steps:
-            stepper(i)
-        self.last_graph = stepper.graph
+            steppers[i](i)
+        self.last_graphs = [steppers[first].graph for first, _, _ in segments]
+        self.last_graph = self.last_graphs[-1]
         return latents
 
     def _window_kwargs(self, T, size, stride, vace_context, tea_cache=None):
@@ -576,14 +628,15 @@ class WanVideoPipeline:
         if len(plan.windows) > 1:
             if tea_cache is not None:
                 raise NotImplementedError("tea_cache_l1_thresh with a temporal sliding window is not supported")
-            if vace_context is not None and self.vace is not None:
+            if vace_context is not None and (self.vace is not None or
+                                             (self.dit2 is not None and self.vace2 is not None)):
                 kw["vace_context_windows"] = slice_windows(vace_context.to(self.device), plan)
         return kw
 
     def denoise_unipc(self, latents, context_posi, context_nega, vace_context=None, vace_scale=1.0,
                       cfg_scale=1.2, num_inference_steps=4, sigma_shift=2.0, slg_blocks=(), slg_range=(0.2, 0.7),
                       progress_bar_cmd=None, input_latents=None, forward_step=None, skip_backward_step=None,
-                      sliding_window_size=None, sliding_window_stride=None):
+                      sliding_window_size=None, sliding_window_stride=None, switch_DiT_boundary=0.875):
         """Config 5's sampler (ditto_comfyui_workflow.json WanVideoSampler 4 / 1.2 / 2.0 / unipc with
         WanVideoSLG): FlowUniPCMultistepScheduler (vstyler.unipc) on fp32 latents, CFG as one
         batch-2 forward, skip-layer guidance on the uncond sample for step fractions in slg_range.
@@ -595,7 +648,16 @@ class WanVideoPipeline:
         (both counted from the schedule's end, in [1, n]); a step's SLG fraction stays its index in the
         full schedule over n.
 
-        sliding_window_size / sliding_window_stride: as in denoise."""
+        sliding_window_size / sliding_window_stride: as in denoise.
+
+        Two experts (dit2 set): experts.plan_experts over the executed timesteps[first:] (the
+        scheduler's int64 values against switch_DiT_boundary * 1000), cfg_scale a number or a
+        (low_noise, high_noise) pair as in denoise.  An expert no executed step selects is never
+        touched: the Wan2.2 enhancer pass (40 steps, shift 12, forward_step = skip_backward_step = 5)
+        has every timestep below 875 and runs with pipe.dit = None."""
+        from .experts import expert_cfg_scales, plan_experts
+        has2 = self.dit2 is not None
+        scales = expert_cfg_scales(cfg_scale, has2)
         window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context)
         from .unipc import FlowUniPCMultistepScheduler, cast
         sched = FlowUniPCMultistepScheduler(shift=1.0)
@@ -610,8 +672,12 @@ class WanVideoPipeline:
                 if not isinstance(val, int) or isinstance(val, bool) or not 1 <= val <= n:
                     raise ValueError(f"{name} must be an integer in [1, {n}], got {val!r}")
             first = n - skip_backward_step
-        use_cfg = cfg_scale != 1.0
-        ctx = torch.cat([context_posi, context_nega], 0) if use_cfg else context_posi
+        expert_of = {}
+        for lo, hi, e in plan_experts(sched.timesteps[first:], switch_DiT_boundary, has2):
+            for i in range(first + lo, first + hi + 1):
+                expert_of[i] = e
+        any_cfg = any(scales[e - 1] != 1.0 for e in expert_of.values())
+        ctx_cfg = torch.cat([context_posi, context_nega], 0) if any_cfg else None
         lat32 = latents.to(device=self.device, dtype=torch.float32).contiguous().clone()
         if input_latents is not None:
             x0 = input_latents.to(device=self.device, dtype=torch.float32).contiguous()
@@ -627,12 +693,16 @@ class WanVideoPipeline:
             cast(lat32, lat16)
             frac = i / n
             slg = tuple(slg_blocks) if slg_range[0] <= frac <= slg_range[1] else ()
-            v = self.model_fn(dit=self.dit, vace=self.vace, latents=lat16, timestep=t.reshape(1).to(
+            dit, vace = self._expert(expert_of[i])
+            scale = scales[expert_of[i] - 1]
+            use_cfg = scale != 1.0
+            ctx = ctx_cfg if use_cfg else context_posi
+            v = self.model_fn(dit=dit, vace=vace, latents=lat16, timestep=t.reshape(1).to(
                 dtype=BF16, device=self.device), context=ctx, vace_context=vace_context, vace_scale=vace_scale,
                 use_unified_sequence_parallel=self.use_unified_sequence_parallel, sp_group=self.sp_group,
                 slg_blocks=slg, **window_kw)
             v16.zero_()
-            K.cfg_euler(v[0:1], v[1:2] if use_cfg else None, v16, cfg_scale, 1.0)   # v16 = cfg combine
+            K.cfg_euler(v[0:1], v[1:2] if use_cfg else None, v16, scale, 1.0)   # v16 = cfg combine
             cast(v16, v32)
             lat32 = sched.step(v32, t, lat32)[0]
         return cast(lat32, torch.empty(lat32.shape, dtype=BF16, device=self.device))
@@ -649,7 +719,8 @@ class WanVideoPipeline:
                  prompt_emb=None, negative_prompt_emb=None, vace_context=None, output_type="video",
                  input_latents=None, **kwargs):
         """wan_video_new.py:416-560 for the Ditto path (T2V/VACE/video-to-video, no image/audio/camera
-        inputs).  input_video (or its precomputed latents input_latents (1, 16, T', h, w)) with
+        inputs).  With dit2 loaded the steps below switch_DiT_boundary run on dit2 / vace2 and cfg_scale
+        may be a (low_noise, high_noise) pair (denoise).  input_video (or its precomputed latents input_latents (1, 16, T', h, w)) with
         denoising_strength < 1 starts the loop from the video's latents re-noised to the first sigma
         of the shortened schedule (WanVideoUnit_InputVideoEmbedder, :591-614)."""
         for name, val in (("input_image", input_image), ("end_image", end_image),
@@ -659,6 +730,10 @@ class WanVideoPipeline:
         if input_video is not None and input_latents is not None:
             raise ValueError("pass input_video or its precomputed input_latents, not both")
         check_window_args(sliding_window_size, sliding_window_stride)
+        from .experts import expert_cfg_scales
+        scales = expert_cfg_scales(cfg_scale, self.dit2 is not None)
+        if tea_cache_l1_thresh is not None and self.dit2 is not None:
+            raise NotImplementedError("tea_cache_l1_thresh with a second expert (dit2) is not supported")
         height, width, num_frames = self.check_resize_height_width(height, width, num_frames)
         T = (num_frames - 1) // 4 + 1
         # WanVideoUnit_NoiseInitializer (wan_video_new.py:578-587): f reference images add f latent
@@ -678,7 +753,7 @@ class WanVideoPipeline:
             start = self.scheduler.add_noise(input_latents, noise.contiguous(), self.scheduler.timesteps[0])
         if prompt_emb is None:
             prompt_emb = self.encode_prompt(prompt)
-        if negative_prompt_emb is None and cfg_scale != 1.0:
+        if negative_prompt_emb is None and any(c != 1.0 for c in scales):
             negative_prompt_emb = self.encode_prompt(negative_prompt)
         if vace_context is None and (vace_video is not None or vace_video_mask is not None or nref):
             vace_context = self.encode_vace(vace_video, vace_video_mask, height, width, num_frames, tiled,
@@ -692,7 +767,7 @@ class WanVideoPipeline:
                                None if vace_context is None else vace_context.to(self.device), vace_scale,
                                cfg_scale, num_inference_steps, sigma_shift, denoising_strength, progress_bar_cmd,
                                tea_cache=tea_cache, sliding_window_size=sliding_window_size,
-                               sliding_window_stride=sliding_window_stride)
+                               sliding_window_stride=sliding_window_stride, switch_DiT_boundary=switch_DiT_boundary)
         self.last_tea_cache = tea_cache
         if nref:                                            # :545-550
             latents = latents[:, :, nref:].contiguous()
@@ -702,6 +777,60 @@ class WanVideoPipeline:
             raise RuntimeError("VAE decode requires a loaded Wan2.1 VAE (or use output_type='latents')")
         video = self.vae.decode(latents, device=self.device, tiled=tiled, tile_size=tile_size, tile_stride=tile_stride)
         return self.vae_output_to_video(video, output_type)
+
+    @torch.no_grad()
+    def enhance(self, video, prompt=None, negative_prompt="", height=720, width=1280, num_inference_steps=40,
+                sigma_shift=12.0, cfg_scale=(3.0, 4.0), switch_DiT_boundary=0.875, forward_step=5,
+                skip_backward_step=5, seed=None, tiled=True, tile_size=(30, 52), tile_stride=(15, 26),
+                prompt_emb=None, negative_prompt_emb=None, output_type="video"):
+        """The reference's "Denoising Enhancing" mode (denoising_enhancing/video_enhancing_batch.py:43-83,
+        395-419 around wan/text2video.py:297-401 with wan/configs/wan_t2v_A14B.py): frames in, frames
+        out.  The video is resized to height x width (nearest neighbour, vs_resize_nearest_u8, when it is
+        not that size already), VAE-encoded, re-noised at timesteps[-forward_step] of the UniPC schedule
+        and denoised over timesteps[-skip_backward_step:] with the two Wan2.2 A14B experts (dit: high
+        noise, dit2: low noise; per-expert guidance cfg_scale = (low_noise, high_noise)), then decoded.
+        With the defaults every executed timestep is below the boundary, so only dit2 runs (pipe.dit may
+        be None).  The frame count must be 4k + 1 (the reference does not round it).
+
+        Deviations from the reference's enhancer:
+          * the noise comes from generate_noise (this build's CPU generator); the reference seeds a
+            device generator;
+          * the negative prompt defaults to "" (the reference's config carries a fixed string);
+          * frames are normalised by this build's preprocess_video (the DiffSynth pipeline's bf16
+            rounding points), not by the enhancer's fp32 read_video;
+          * the DiT forward keeps this build's DiffSynth rounding points; parity with the official
+            Wan2.2 module (fp32 residual stream, fp32 modulation) is unpinned;
+          * the DPM++ solver is not built (UniPC only).
+
+        output_type: "video" (PIL images), "u8" ((T, H, W, 3) uint8 device tensor) or "latents"."""
+        from .experts import expert_cfg_scales
+        from .vae import frames_to_u8, preprocess_video
+        frames = frames_to_u8(video, self.device)
+        if frames.shape[0] % 4 != 1:
+            raise ValueError(f"enhance: the video must have 4k + 1 frames, got {frames.shape[0]}")
+        if height % 8 or width % 8:
+            raise ValueError(f"enhance: height and width must be multiples of 8, got {height}x{width}")
+        scales = expert_cfg_scales(cfg_scale, self.dit2 is not None)
+        if self.vae is None:
+            raise RuntimeError("enhance requires a loaded Wan2.1 VAE")
+        if tuple(frames.shape[1:3]) != (height, width):
+            frames = K.resize_nearest_u8(frames, height, width)
+        x0 = self.vae.encode(preprocess_video(frames), self.device, tiled=tiled, tile_size=tile_size,
+                             tile_stride=tile_stride)
+        noise = self.generate_noise(tuple(x0.shape), seed=seed)
+        if prompt_emb is None:
+            prompt_emb = self.encode_prompt(prompt)
+        if negative_prompt_emb is None and any(c != 1.0 for c in scales):
+            negative_prompt_emb = self.encode_prompt(negative_prompt)
+        latents = self.denoise_unipc(noise, prompt_emb.to(self.device), None if negative_prompt_emb is None else
+                                     negative_prompt_emb.to(self.device), cfg_scale=cfg_scale,
+                                     num_inference_steps=num_inference_steps, sigma_shift=sigma_shift,
+                                     input_latents=x0, forward_step=forward_step,
+                                     skip_backward_step=skip_backward_step, switch_DiT_boundary=switch_DiT_boundary)
+        if output_type == "latents":
+            return latents
+        out = self.vae.decode(latents, device=self.device, tiled=tiled, tile_size=tile_size, tile_stride=tile_stride)
+        return self.vae_output_to_video(out, output_type)
 
     def encode_prompt(self, prompt):
         if self.text_encoder is None or self.prompter is None:

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import wan_oracle as O
+import gpu_util as U
 from gpu_util import BF16, err
 
 pytestmark = pytest.mark.gpu
@@ -599,3 +600,157 @@ def test_attention_item_queue_matches_static_lists(K, opt, B, Sq, Skv, H):
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
     bufs = [b for (kind, _, _), b in K._SPLIT_WS.items() if kind == 5]
     assert bufs and all(int(b.count_nonzero()) == 0 for b in bufs)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Row kernels at their edges: dims around the 128-thread chunk column and the 5- / 8-chunk
+# instantiations, one shift / scale pair per row (rows_per_batch = 1), x a column slice of a wider
+# buffer and out with ldo > dim (the outer columns must keep their bits).  The reference is the
+# oracle chain with the statistics in float64 and the same bf16 rounding points; per element
+# |got - ref| <= 2^-7 (|n (1 + scale)| + |ref|) -- one bf16 ulp at each of the two places where an
+# fp32-level difference in n can flip a rounding -- and >= 99 % of the elements bit-identical
+# (gpu_util.RowTally; tests/test_kernel_refs_cpu.py holds the oracle's own fp32 chain to the same bar).
+# ---------------------------------------------------------------------------------------------------
+
+def _sliced(x):
+    """x [rows, dim] on the device as the middle column slice of a [rows, 3 dim] NaN-filled buffer."""
+    rows, dim = x.shape
+    wide = U.sentinel((rows, 3 * dim))
+    wide[:, dim:2 * dim] = x.cuda()
+    return wide, wide[:, dim:2 * dim]
+
+
+def _outer_untouched(wide, dim):
+    return U.untouched(wide[:, :dim]) and U.untouched(wide[:, 2 * dim:])
+
+
+@pytest.mark.parametrize("D", U.ROW_LN_DIMS)
+def test_layernorm_modulate_edges(K, D):
+    tally = U.RowTally(f"layernorm_modulate dim {D}")
+    for rows in (1, 5):
+        x, mod, w, b = U.row_inputs(rows, D, seed=1)
+        wide, xs = _sliced(x)
+        md = mod.cuda()
+        ob = U.sentinel((rows + 1, D + 8))
+        K.layernorm_modulate(xs, ob[:rows, :D], 1e-6, shift=md[:, 0], scale=md[:, 1], mod_bstride=2 * D, rows_per_batch=1)
+        torch.cuda.synchronize()
+        ref, bound = U.ln_modulate_ref(x, mod[:, 0], mod[:, 1])
+        tally.check(ob[:rows, :D], ref, bound, f"modulate rows {rows}")
+        assert U.untouched(ob[:rows, D:]) and U.untouched(ob[rows:]) and U.same_bits(xs, x) and _outer_untouched(wide, D)
+        ob = U.sentinel((rows + 1, D + 8))
+        K.layernorm_modulate(xs, ob[:rows, :D], 1e-6, weight=w.cuda(), bias=b.cuda())
+        torch.cuda.synchronize()
+        ref, bound = U.ln_affine_ref(x, w, b)
+        tally.check(ob[:rows, :D], ref, bound, f"affine rows {rows}")
+        assert U.untouched(ob[:rows, D:]) and U.untouched(ob[rows:])
+    tally.finish()
+
+
+@pytest.mark.parametrize("D", U.ROW_LN_DIMS)
+@pytest.mark.parametrize("form", ["modulate", "affine"])
+def test_layernorm_modulate_fp8_edges(K, D, form):
+    """Bit-identical to layernorm_modulate followed by quant_fp8_rows, at the edge dims, one modulation
+    pair per row, x a column slice and x8 with ld8 > dim (its outer bytes unchanged)."""
+    for rows in (1, 5):
+        x, mod, w, b = U.row_inputs(rows, D, seed=2)
+        mod[:, 1, :8] = 3000.0                     # outputs above 448: a per-row scale > 1
+        w[:8] = 3000.0
+        _, xs = _sliced(x)
+        md = mod.cuda()
+        ln = dict(shift=md[:, 0], scale=md[:, 1], mod_bstride=2 * D, rows_per_batch=1) if form == "modulate" else \
+            dict(weight=w.cuda(), bias=b.cuda())
+        h = torch.empty(rows, D, dtype=BF16, device="cuda")
+        K.layernorm_modulate(xs, h, 1e-6, **ln)
+        ref8 = torch.empty(rows, D, dtype=torch.uint8, device="cuda")
+        refs = torch.empty(rows, dtype=torch.float32, device="cuda")
+        K.quant_fp8_rows(h, ref8, refs)
+        x8w = torch.full((rows + 1, D + 16), 0xA5, dtype=torch.uint8, device="cuda")
+        sc = U.sentinel(rows + 3, torch.float32)
+        K.layernorm_modulate_fp8(xs, x8w[:rows, :D], sc[:rows], 1e-6, **ln)
+        torch.cuda.synchronize()
+        assert torch.equal(sc[:rows], refs) and U.untouched(sc[rows:]), (rows, form)
+        assert torch.equal(x8w[:rows, :D], ref8), (rows, form)
+        assert bool((x8w[:rows, D:] == 0xA5).all()) and bool((x8w[rows:] == 0xA5).all())
+        assert (refs > 1).all()
+
+
+@pytest.mark.parametrize("D", U.ROW_LN_DIMS)
+@pytest.mark.parametrize("mode", ["gate_res", "gate_res_hint", "res"])
+def test_residual_layernorm_edges(K, D, mode):
+    """vs_residual_layernorm == the residual epilogue on a staged y, then vs_layernorm_modulate, bit for
+    bit, at the edge dims with strided x / y / out and one gate and modulation row per row.  The
+    epilogue's row update: vs_gemm with an identity weight where dim % 64 == 0 (as the test above),
+    else the same expression as torch bf16 ops on the device."""
+    f = lambda t: t.float()  # noqa: E731
+    for rows in (1, 5):
+        x0, mod, w, b = U.row_inputs(rows, D, seed=3)
+        g = torch.Generator().manual_seed(D + rows)
+        y = (0.5 * torch.randn(rows, D, generator=g)).to(BF16)
+        gate = (0.5 * torch.randn(rows, D, generator=g)).to(BF16).cuda()
+        hint = torch.randn(rows, D, generator=g).to(BF16).cuda()
+        _, ys = _sliced(y)
+        md, wd, bd = mod.cuda(), w.cuda(), b.cuda()
+        x1 = x0.cuda()
+        if D % 64 == 0:
+            eye = torch.eye(D, dtype=BF16, device="cuda")
+            if mode == "res":
+                K.gemm(ys, eye, x1, epilogue=K.VS_EPI_RES, residual=x1, alpha=0.75)
+            else:
+                hk = dict(hint=hint, hint_scale=0.5) if mode == "gate_res_hint" else {}
+                K.gemm(ys, eye, x1, epilogue=K.VS_EPI_GATE_RES, residual=x1, gate=gate, gate_bstride=D,
+                       rows_per_batch=1, **hk)
+            del eye
+        elif mode == "res":
+            x1 = (f(x1) + (0.75 * f(ys)).to(BF16).float()).to(BF16)
+        else:
+            x1 = (f(x1) + (f(gate) * f(ys)).to(BF16).float()).to(BF16)
+            if mode == "gate_res_hint":
+                x1 = (f(x1) + (f(hint) * 0.5).to(BF16).float()).to(BF16)
+        h1 = torch.empty(rows, D, dtype=BF16, device="cuda")
+        ln = dict(shift=md[:, 0], scale=md[:, 1], mod_bstride=2 * D, rows_per_batch=1) if mode == "res" else \
+            dict(weight=wd, bias=bd)
+        K.layernorm_modulate(x1, h1, 1e-6, **ln)
+        wide, x2 = _sliced(x0)
+        ob = U.sentinel((rows + 1, D + 8))
+        if mode == "res":
+            K.residual_layernorm(ys, x2, ob[:rows, :D], 1e-6, epilogue=K.VS_EPI_RES, alpha=0.75, **ln)
+        else:
+            hk = dict(hint=hint, hint_scale=0.5) if mode == "gate_res_hint" else {}
+            K.residual_layernorm(ys, x2, ob[:rows, :D], 1e-6, epilogue=K.VS_EPI_GATE_RES, gate=gate, gate_bstride=D,
+                                 gate_rows=1, **ln, **hk)
+        torch.cuda.synchronize()
+        assert U.same_bits(x2, x1), (rows, mode)
+        assert U.same_bits(ob[:rows, :D], h1), (rows, mode)
+        assert U.untouched(ob[:rows, D:]) and U.untouched(ob[rows:]) and _outer_untouched(wide, D)
+
+
+@pytest.mark.parametrize("D", U.ROW_RMS_DIMS)
+def test_rmsnorm_rope_edges(K, D):
+    """In place on the q and k column slices of a fused q|k|v buffer (ldx = 3 D, as models.py runs it)
+    with RoPE on a (2, 3, 5) grid at token_offset 13 (the rows cross a frame and a line of the grid);
+    the v slice keeps its bits.  Then without RoPE.  Against the oracle chain with the mean square in
+    float64 and the rotation in complex128 (bounds at gpu_util.rms_rope_ref)."""
+    from vstyler.models import rope_table
+    grid, off, H = (2, 3, 5), 13, D // 128
+    table = rope_table(device="cuda")
+    tally = U.RowTally(f"rmsnorm_rope dim {D}")
+    for rows in (1, 5):
+        x, _, w, _ = U.row_inputs(rows, 3 * D, seed=4)
+        w = w[:D].contiguous()
+        qkv = x.cuda()
+        freqs = O.rope_freqs(*grid)[off:off + rows]
+        for i in range(2):
+            K.rmsnorm_rope(qkv[:, i * D:(i + 1) * D], w.cuda(), 1e-6, rope=table, grid=grid, rows_per_batch=rows,
+                           token_offset=off)
+        torch.cuda.synchronize()
+        for i in range(2):
+            ref, bound = U.rms_rope_ref(x[:, i * D:(i + 1) * D], w, 1e-6, freqs, H)
+            tally.check(qkv[:, i * D:(i + 1) * D], ref, bound, f"rope rows {rows} slice {i}")
+        assert U.same_bits(qkv[:, 2 * D:], x[:, 2 * D:]), rows
+        qkv = x.cuda()
+        K.rmsnorm_rope(qkv[:, D:2 * D], w.cuda(), 1e-6)
+        torch.cuda.synchronize()
+        ref, bound = U.rms_rope_ref(x[:, D:2 * D], w)
+        tally.check(qkv[:, D:2 * D], ref, bound, f"plain rows {rows}")
+        assert U.same_bits(qkv[:, :D], x[:, :D]) and U.same_bits(qkv[:, 2 * D:], x[:, 2 * D:])
+    tally.finish()

@@ -104,7 +104,7 @@ int vs_gemm_split_plan(int m, int n, int k, int cus, int* out);
  * `epilogue`: 0 = the MFMA kernels with the epilogue fused -- the only route of this build (r5: the
  * vendor-library route and its separate epilogue pass are gone) -- or -VS_E_INVALID for non-positive
  * sizes or an unknown epilogue.  vs_gemm_route(m, n, k) = vs_gemm_route_epi(m, n, k, VS_EPI_BIAS, 0).
- * Host-only.  (A binding fuses a residual epilogue with the next LayerNorm only on a route != 0.)
+ * Host-only.
  */
 int vs_gemm_route(int m, int n, int k);
 int vs_gemm_route_epi(int m, int n, int k, int epilogue, int fp8);
@@ -226,12 +226,12 @@ int vs_layernorm_modulate_fp8(const void* x, long long ldx, void* x8, long long 
 
 /*
  * x = epilogue(y, x) then out = vs_layernorm_modulate(x): the gate-residual / residual epilogue of a
- * projection whose bf16(A W^T + bias) was staged in y, fused with the
+ * projection whose bf16(A W^T + bias) the caller holds in y, fused with the
  * LayerNorm [+ affine] [+ modulate] that reads the updated row next (wan_video_dit.py:225-228).
  * epilogue: VS_EPI_GATE_RES (epi->gate, gate_bstride, rows_per_batch, optional hint) or VS_EPI_RES
  * (epi->alpha); epi->residual is ignored (x is the residual).  Same rounding points as vs_gemm's
- * epilogue followed by vs_layernorm_modulate: bit-identical to the two calls.  (Used with a GEMM route
- * that stages its output, vs_gemm_route_epi != 0; none in this build.)
+ * epilogue followed by vs_layernorm_modulate: bit-identical to the two calls.  A standalone row op:
+ * vs_gemm fuses these epilogues itself, so the Python model does not call it.
  */
 int vs_residual_layernorm(const void* y, long long ldy, void* x, long long ldx, void* out, long long ldo, int rows,
                           int dim, int epilogue, const vs_epilogue* epi, int rows_per_batch, const void* shift,

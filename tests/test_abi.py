@@ -53,6 +53,18 @@ def test_invalid_arguments_rejected_before_launch():
     assert lib.vs_gemm(fake, 64, fake, 64, fake, 8, 8, 8, 64, 9, ep, None, 0, None, 0, 0, None) == 1
     # gate-residual without residual
     assert lib.vs_gemm(fake, 64, fake, 64, fake, 8, 8, 8, 64, 3, ep, None, 0, None, 0, 0, None) == 1
+    # every operand rule of vs_gemm, one at a time: sizes, N % 4, leading dimensions (below the extent,
+    # lda / ldw % 8, ldc % 4), base alignment; then its LoRA phase (k2 % 64, null / short / misaligned)
+    ok = dict(a=fake, lda=64, w=fake, ldw=64, c=fake, ldc=8, m=8, n=8, k=64, a2=fake, lda2=64, w2=fake, ldw2=64, k2=64)
+    bad = [dict(a=None), dict(w=None), dict(c=None), dict(m=0), dict(n=0), dict(k=0), dict(n=6, ldc=6),
+           dict(lda=32), dict(ldw=32), dict(ldc=4), dict(lda=68), dict(ldw=68), dict(ldc=10),
+           dict(a=fake + 8), dict(w=fake + 8), dict(c=fake + 4),
+           dict(k2=48), dict(k2=-64), dict(a2=None), dict(w2=None), dict(lda2=32), dict(ldw2=32), dict(lda2=68),
+           dict(ldw2=68), dict(a2=fake + 8), dict(w2=fake + 2)]
+    for kw in bad:
+        g = dict(ok, **kw)
+        assert lib.vs_gemm(g["a"], g["lda"], g["w"], g["ldw"], g["c"], g["ldc"], g["m"], g["n"], g["k"], 0, ep,
+                           g["a2"], g["lda2"], g["w2"], g["ldw2"], g["k2"], None) == 1, kw
     # head_dim != 128 is unsupported, misaligned stride invalid
     assert lib.vs_attn_fwd(fake, fake, fake, fake, 1, 16, 16, 1, 64, 64, 64, 64, 64, 0, 0, 0, 0, 1.0, None) == 3
     assert lib.vs_attn_fwd(fake, fake, fake, fake, 1, 16, 16, 1, 128, 130, 128, 128, 128, 0, 0, 0, 0, 1.0, None) == 1

@@ -98,20 +98,3 @@ def test_hotload_refuses_fp8_layers_atomically():
     assert hotload_lora(blk, lora) == 2
     assert blk.self_attn.q.lora_A.shape == (64, 256) and blk.cross_attn.o.lora_B.shape == (256, 64)
 
-
-def test_residual_ln_fusion_follows_the_gemm_route(monkeypatch):
-    """models._fusable_lt asks vs_gemm_route_epi for the residual epilogue the unfused path would run:
-    the residual + LayerNorm fusion (a staged GEMM output) is taken exactly when that GEMM would run
-    as a staged product + epilogue pass -- never with the product library, whose GEMMs all fuse their
-    epilogue (r5, include/vstyler.h), so the model never stages an output.  Host-only."""
-    from vstyler import kernels as K
-    from vstyler.models import _fusable_lt, quantize_fp8_
-    o = nn.Linear(5120, 5120, dtype=BF16)              # o-proj / cross-attention o shape
-    down = nn.Linear(13824, 5120, dtype=BF16)          # FFN-down
-    for M in (59280, 7410):
-        for lin, ep in ((o, K.VS_EPI_GATE_RES), (o, K.VS_EPI_RES), (down, K.VS_EPI_GATE_RES)):
-            assert _fusable_lt(lin, M, ep) == K.gemm_route(M, lin.out_features, lin.in_features, epilogue=ep)
-            assert _fusable_lt(lin, M, ep) is False
-    blk, _ = _block()
-    quantize_fp8_(blk)
-    assert _fusable_lt(blk.self_attn.o, 59280, K.VS_EPI_GATE_RES) is False

@@ -156,8 +156,9 @@ __global__ __launch_bounds__(RT) void ln_modulate_kernel(
     }
 }
 
-// Gated / plain residual add of a staged projection y (the hipBLASLt route's bf16(A W^T + bias))
-// into x, then LayerNorm [+ affine] [+ modulate] of the updated row into out: the vs_gemm epilogue
+// vs_residual_layernorm, a standalone fused row op (the model does not call it: its GEMMs fuse the
+// residual epilogue themselves).  Gated / plain residual add of a bf16 projection y = bf16(A W^T + bias)
+// the caller holds into x, then LayerNorm [+ affine] [+ modulate] of the updated row into out: the vs_gemm epilogue
 // (VS_EPI_GATE_RES: x = bf16(x + bf16(gate*y)) [+ bf16(hint*s)]; VS_EPI_RES: x = bf16(x + bf16(alpha*y)))
 // followed by ln_modulate_kernel's arithmetic on the stored bf16 row -- the same rounding points as
 // the two separate passes, one read of x instead of two (wan_video_dit.py:225-228).

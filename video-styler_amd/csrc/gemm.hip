@@ -215,8 +215,8 @@ __global__ __launch_bounds__(NTHR, 2) void gemm_bf16_tn(
 
 
 // ---------------------------------------------------------------------------------------------
-// 256x256 tiles (gemm_bf16_tn_8p, gemm_fp8_tn_8p): shared tile order, split-tail combine, epilogue
-// pass of the hipBLASLt route.
+// 256x256 tiles (gemm_bf16_tn_8p, gemm_fp8_tn_8p, the 4-wave kernels): shared tile order, split-tail
+// combine.
 // ---------------------------------------------------------------------------------------------
 #ifndef VS_GEMM_GM
 #define VS_GEMM_GM 4            // M-tiles per raster group (L2 reuse of the weight tile)
@@ -236,11 +236,13 @@ __device__ __forceinline__ void tile_of(int pid, int ntm, int ntn, int GM, int& 
 }
 
 // Split-tail combine: one thread per (tail tile, row, 4 columns): sum the ksplit fp32 partials in
-// piece order, then the same epilogue as the unsplit kernel
+// piece order, then the same epilogue as the unsplit kernel.  The fp8 scales (both null for bf16):
+// (sum * scale_w[n]) * scale_a[m], the order of every scaled route (the column scale of
+// vs_gemm_fp8_ws first, then the unscaled kernel's own arithmetic)
 __global__ __launch_bounds__(256) void gemm_split_combine(const float* __restrict__ part, bf16_t* C, long long ldc,
                                                           int M, int N, Epi ep, int ntm, int ntn, int nmain,
-                                                          int ntail, int ksplit,
-                                                          const float* __restrict__ scale_a = nullptr) {
+                                                          int ntail, int ksplit, const float* __restrict__ scale_a,
+                                                          const float* __restrict__ scale_w) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long long)ntail * BT * (BT / 4)) return;
     const int t = (int)(idx / (BT * (BT / 4)));
@@ -253,30 +255,8 @@ __global__ __launch_bounds__(256) void gemm_split_combine(const float* __restric
     const float* pp = part + (long long)t * ksplit * BT * BT + row * BT + 4 * c4;
     f32x4_t a = *reinterpret_cast<const f32x4_t*>(pp);
     for (int j = 1; j < ksplit; ++j) a += *reinterpret_cast<const f32x4_t*>(pp + (long long)j * BT * BT);
+    if (scale_w) a *= *reinterpret_cast<const f32x4_t*>(scale_w + n);
     if (scale_a) a *= scale_a[m];
-    epilogue_store(a, m, n, C, ldc, ep);
-}
-
-// the same with the fp8 weight scale (vs_gemm_fp8_ws): (sum * scale_w[n]) * scale_a[m], the order of
-// every scaled route (the column scale first, then the unscaled kernel's own arithmetic)
-__global__ __launch_bounds__(256) void gemm_split_combine_ws(const float* __restrict__ part, bf16_t* C, long long ldc,
-                                                             int M, int N, Epi ep, int ntm, int ntn, int nmain,
-                                                             int ntail, int ksplit, const float* __restrict__ scale_a,
-                                                             const float* __restrict__ scale_w) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)ntail * BT * (BT / 4)) return;
-    const int t = (int)(idx / (BT * (BT / 4)));
-    const int rem = (int)(idx % (BT * (BT / 4)));
-    const int row = rem / (BT / 4), c4 = rem % (BT / 4);
-    int tm, tn;
-    tile_of(nmain + t, ntm, ntn, ep.gm, tm, tn);
-    const int m = tm * BT + row, n = tn * BT + 4 * c4;
-    if (m >= M || n >= N) return;
-    const float* pp = part + (long long)t * ksplit * BT * BT + row * BT + 4 * c4;
-    f32x4_t a = *reinterpret_cast<const f32x4_t*>(pp);
-    for (int j = 1; j < ksplit; ++j) a += *reinterpret_cast<const f32x4_t*>(pp + (long long)j * BT * BT);
-    a *= *reinterpret_cast<const f32x4_t*>(scale_w + n);
-    a *= scale_a[m];
     epilogue_store(a, m, n, C, ldc, ep);
 }
 
@@ -2199,15 +2179,15 @@ KSplit plan_ksplit_held(int ntiles, int nh, int cus, int step) {
     return p;
 }
 
-// Routing (r5): every GEMM of the path runs on the kernels of this file.  r1-r4 sent the plain-bias
-// q|k|v / cross-q projections, the GELU FFN-up and the context GEMMs at SP = 1 to a private copy of
-// ROCm's hipBLASLt (+ a separate epilogue pass), which beat the hand-written kernels there (r4: q|k|v
-// 1551 vs 1501 TF/s).  With the XCD tile queues the 4-wave kernel matches it on q|k|v (1529-1544 vs
-// 1547-1556 TF/s, within run-to-run spread), leads on every fused-epilogue shape (FFN-up 1488-1496
-// vs 1410-1413, o-proj 1438-1441 vs 1291-1296), reads fewer L2->fabric bytes on q|k|v (16.8 vs
-// 17.9 GB per dispatch), and the whole step is as fast: 0.3906 / 0.3882 vs 0.3888 / 0.3881 steps/s
-// with the library routes, same box, interleaved (profiles/r5/queue_ab_s2.log,
-// pmc_fetch_queue_s2.txt, bench_own_vs_lt_ab_s2.log).  r6 removed the A/B build's library route.
+// Routing (r5): every GEMM of the path runs on the kernels of this file, its epilogue fused (r1-r4 sent
+// the plain-bias projections to a vendor library + a separate epilogue pass; r5 replaced it, r6
+// removed it).  What decided it: with the XCD tile queues the 4-wave kernel runs q|k|v at
+// 1529-1544 TF/s (the library: 1547-1556, within run-to-run spread), leads on every fused-epilogue
+// shape (FFN-up 1488-1496 vs 1410-1413, o-proj 1438-1441 vs 1291-1296), reads fewer L2->fabric
+// bytes on q|k|v (16.8 vs 17.9 GB per dispatch), and the whole step is as fast: 0.3906 / 0.3882 vs
+// 0.3888 / 0.3881 steps/s, same box, interleaved (profiles/r5/queue_ab_s2.log,
+// pmc_fetch_queue_s2.txt, bench_own_vs_lt_ab_s2.log); fp8: q|k|v 3013 vs 3068 TF/s, FFN-up 2839 vs
+// 2500, o-proj 2652 vs 2225 (profiles/r5/gemm_fp8_queue_ab_s1.log).
 
 // which 256x256 kernel runs the un-split-phase (k2 == 0) GEMMs: the 4-wave kernel (default since
 // r4: 1-5 % over the 8-phase kernel on every 14B shape at 59 280 and 7410 rows) | VS_OPT_GEMM_KERNEL 8
@@ -2261,22 +2241,112 @@ static int fill_epi(Epi& ep, int epilogue, const vs_epilogue* epi, int m, int n)
     return VS_OK;
 }
 
+// the main operands A [m, k] / W [n, k] (K-contiguous rows, 16-B aligned: K a multiple of kgran
+// elements, lda / ldw of ldmask + 1: 64 / 7 for bf16, 128 / 15 for fp8) and C [m, n] bf16
+static bool main_operands_ok(const void* a, long long lda, const void* w, long long ldw, const void* c, long long ldc,
+                             int m, int n, int k, int kgran, int ldmask) {
+    if (!a || !w || !c || m <= 0 || n <= 0 || k <= 0) return false;
+    if (k % kgran || n % 4) return false;
+    if (lda < k || ldw < k || ldc < n || (lda & ldmask) || (ldw & ldmask) || (ldc & 3)) return false;
+    return aligned16(a) && aligned16(w) && aligned8(c);
+}
+
+// the un-merged LoRA phase A2 [m, k2] / W2 [n, k2] (bf16): k2 a multiple of 64, 0 for none
+static bool lora_operands_ok(const void* a2, long long lda2, const void* w2, long long ldw2, int k2) {
+    if (k2 < 0 || k2 % BK) return false;
+    if (k2 == 0) return true;
+    if (!a2 || !w2 || lda2 < k2 || ldw2 < k2 || (lda2 & 7) || (ldw2 & 7)) return false;
+    return aligned16(a2) && aligned16(w2);
+}
+
+// 16-B epilogue accesses (the WIDE instantiations) when every epilogue operand allows them
+static bool epi_wide(const Epi& ep, int n, const void* c, long long ldc) {
+    return n % 8 == 0 && ldc % 8 == 0 && aligned16(c) && (!ep.bias || aligned16(ep.bias)) &&
+           (!ep.res || (ep.ld_res % 8 == 0 && aligned16(ep.res))) &&
+           (!ep.gate || (ep.gate_bstride % 8 == 0 && aligned16(ep.gate))) &&
+           (!ep.hint || (ep.ld_hint % 8 == 0 && aligned16(ep.hint)));
+}
+
+// a split plan with its kind-1 workspace (the fp32 partial tiles) in `part`; whole tiles when the
+// stream has none bound that is large enough
+static KSplit split_tail(const KSplit& plan, hipStream_t stream, float*& part) {
+    part = plan.ntail ? vs_split_workspace(1, (size_t)plan.ntail * plan.ksplit * BT * BT * sizeof(float), stream)
+                      : nullptr;
+    return part ? plan : KSplit{plan.nmain + plan.ntail, 0, 1, 0};
+}
+// the plan of a launch without LoRA phase (VS_OPT_GEMM_SPLIT 0: whole tiles); step: the kernel's K-tile
+static KSplit split_tail(int ntiles, int k, int step, hipStream_t stream, float*& part) {
+    return split_tail(plan_ksplit(ntiles, k / step, vs_cus_for_split(!vs_opt(VS_OPT_GEMM_SPLIT)), step), stream, part);
+}
+
+static int launch_combine(const KSplit& sp, const float* part, void* c, long long ldc, int m, int n, const Epi& ep,
+                          int tm, int tn, const float* scale_a, const float* scale_w, hipStream_t stream) {
+    const long long threads = (long long)sp.ntail * BT * (BT / 4);
+    hipLaunchKernelGGL(gemm_split_combine, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, part,
+                       (bf16_t*)c, ldc, m, n, ep, tm, tn, sp.nmain, sp.ntail, sp.ksplit, scale_a, scale_w);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+
+// the 4-wave instantiations, one per 16-B epilogue mode (index: the mode, 5 = gate-residual + hint;
+// fp8 6: the 8-B path).  (A static table's constant initializer left the kernels' host stubs
+// un-instantiated, hence tables built per call.)
+using K4 = void (*)(const bf16_t*, long long, const bf16_t*, long long, bf16_t*, long long, int, int, int, Epi, int,
+                    int, int, int, int, float*, W4Sched);
+using KF4 = void (*)(const uint8_t*, long long, const float*, const uint8_t*, long long, bf16_t*, long long, int, int,
+                     int, Epi, int, int, int, int, int, float*, W4Sched);
+static K4 bf16_4w(int i) {
+    const K4 t[6] = {gemm_bf16_tn_4w<VS_EPI_BIAS, false>,     gemm_bf16_tn_4w<VS_EPI_GELU, false>,
+                     gemm_bf16_tn_4w<VS_EPI_SILU, false>,     gemm_bf16_tn_4w<VS_EPI_GATE_RES, false>,
+                     gemm_bf16_tn_4w<VS_EPI_RES, false>,      gemm_bf16_tn_4w<VS_EPI_GATE_RES, true>};
+    return t[i];
+}
+static KF4 fp8_4w(int i) {
+    const KF4 t[7] = {gemm_fp8_tn_4w<true, VS_EPI_BIAS, false>, gemm_fp8_tn_4w<true, VS_EPI_GELU, false>,
+                      gemm_fp8_tn_4w<true, VS_EPI_SILU, false>, gemm_fp8_tn_4w<true, VS_EPI_GATE_RES, false>,
+                      gemm_fp8_tn_4w<true, VS_EPI_RES, false>,  gemm_fp8_tn_4w<true, VS_EPI_GATE_RES, true>,
+                      gemm_fp8_tn_4w<false, VS_EPI_BIAS, false>};
+    return t[i];
+}
+static int mode_4w(const Epi& ep) { return (ep.mode == VS_EPI_GATE_RES && ep.hint) ? 5 : ep.mode; }
+
+// every instantiation's dynamic-LDS limit, set once, before the first GEMM launch
+static void set_lds_limits() {
+    static const bool done = [] {
+        const auto set = [](const void* f, int bytes) {
+            (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        };
+        set((const void*)gemm_bf16_tn, 2 * STAGE_BYTES);
+        for (const void* f : {(const void*)gemm_bf16_tn_8p<false, false>, (const void*)gemm_bf16_tn_8p<true, false>,
+                              (const void*)gemm_bf16_tn_8p<false, true>, (const void*)gemm_bf16_tn_8p<true, true>,
+                              (const void*)gemm_fp8_tn_8p<false, false>, (const void*)gemm_fp8_tn_8p<false, false, true>,
+                              (const void*)gemm_fp8_tn_8p<false, true, true>})
+            set(f, LDS8);
+        // the LoRA phase parks the row scales in 1 KB past the buffers, a weight scale the column
+        // scales in a second one
+        for (const void* f : {(const void*)gemm_fp8_tn_8p<true, false>, (const void*)gemm_fp8_tn_8p<true, true>})
+            set(f, LDS8 + 1024);
+        for (const void* f : {(const void*)gemm_fp8_tn_8p<true, false, true>, (const void*)gemm_fp8_tn_8p<true, true, true>})
+            set(f, LDS8 + 2048);
+        for (int i = 0; i < 6; ++i) set((const void*)bf16_4w(i), W4_LDS + 16);
+        for (int i = 0; i < 7; ++i) set((const void*)fp8_4w(i), F4_LDS + 16);
+        return true;
+    }();
+    (void)done;
+}
+
 
 extern "C" int vs_gemm(const void* a, long long lda, const void* w, long long ldw, void* c,
                        long long ldc, int m, int n, int k, int epilogue, const vs_epilogue* epi,
                        const void* a2, long long lda2, const void* w2, long long ldw2, int k2,
-                       void* stream) {
-    if (!a || !w || !c || m <= 0 || n <= 0 || k <= 0) return VS_E_INVALID;
-    if (k % BK || k2 % BK || k2 < 0 || n % 4) return VS_E_INVALID;
-    if (lda < k || ldw < k || ldc < n || (lda & 7) || (ldw & 7) || (ldc & 3)) return VS_E_INVALID;
-    if (!aligned16(a) || !aligned16(w) || !aligned8(c)) return VS_E_INVALID;
-    if (k2 > 0) {
-        if (!a2 || !w2 || lda2 < k2 || ldw2 < k2 || (lda2 & 7) || (ldw2 & 7)) return VS_E_INVALID;
-        if (!aligned16(a2) || !aligned16(w2)) return VS_E_INVALID;
-    }
+                       void* stream_) {
+    if (!main_operands_ok(a, lda, w, ldw, c, ldc, m, n, k, BK, 7)) return VS_E_INVALID;
+    if (!lora_operands_ok(a2, lda2, w2, ldw2, k2)) return VS_E_INVALID;
     Epi ep;
     const int rc = fill_epi(ep, epilogue, epi, m, n);
     if (rc) return rc;
+    const hipStream_t stream = (hipStream_t)stream_;
+    set_lds_limits();
     // 256x256 schedule once the grid holds >= half a round of tiles (the 4-wave kernel from K = 1024:
     // persistent from one full round, its next tile's first K-tiles loading under the current one's
     // epilogue; the 8-phase kernel of the LoRA second phase from K = 4096), 128x128 otherwise
@@ -2287,187 +2357,93 @@ extern "C" int vs_gemm(const void* a, long long lda, const void* w, long long ld
     const long long tiles256 = (long long)((m + BT - 1) / BT) * ((n + BT - 1) / BT);
     const bool big = force ? force == 256
                            : (tiles256 >= 240 && k >= 4096) || (tiles256 >= 128 && k >= 1024 && k2 == 0 && use_4w());
-    if (big) {
-        // 256x256 staggered 8-phase kernel (LoRA second phase included); the last partial round of
-        // tiles runs as K pieces + combine (split tail)
-        const int tm = (m + BT - 1) / BT, tn = (n + BT - 1) / BT;
-        static bool attr8 = false;
-        if (!attr8) {
-            for (const void* f : {(const void*)gemm_bf16_tn_8p<false, false>, (const void*)gemm_bf16_tn_8p<true, false>,
-                                  (const void*)gemm_bf16_tn_8p<false, true>, (const void*)gemm_bf16_tn_8p<true, true>})
-                (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8);
-            attr8 = true;
-        }
-        // 16-B epilogue accesses when every epilogue operand allows them
-        const bool wide = n % 8 == 0 && ldc % 8 == 0 && aligned16(c) &&
-                          (!ep.bias || aligned16(ep.bias)) && (!ep.res || (ep.ld_res % 8 == 0 && aligned16(ep.res))) &&
-                          (!ep.gate || (ep.gate_bstride % 8 == 0 && aligned16(ep.gate))) &&
-                          (!ep.hint || (ep.ld_hint % 8 == 0 && aligned16(ep.hint)));
-        KSplit sp = k2 ? KSplit{tm * tn, 0, 1, 0} : plan_ksplit(tm * tn, k / 64, vs_cus_for_split(!vs_opt(VS_OPT_GEMM_SPLIT)), 64);
-        float* part = nullptr;
-        if (sp.ntail) {
-            part = vs_split_workspace(1, (size_t)sp.ntail * sp.ksplit * BT * BT * sizeof(float), (hipStream_t)stream);
-            if (!part) sp = KSplit{tm * tn, 0, 1, 0};
-        }
-        if (k2 == 0 && wide && use_4w() && vs_opt(VS_OPT_QUEUE) && vs_opt(VS_OPT_PIECE_QUEUE) == 2 &&
-            vs_opt(VS_OPT_GEMM_SPLIT)) {
-            const KSplit held = plan_ksplit_held(tm * tn, k / 64, vs_cus_for_split(false), 64);
-            if (held.ntail > sp.ntail) {
-                float* p2 = vs_split_workspace(1, (size_t)held.ntail * held.ksplit * BT * BT * sizeof(float),
-                                               (hipStream_t)stream);
-                if (p2) {
-                    sp = held;
-                    part = p2;
-                }
-            }
-        }
-        if (k2 == 0 && wide && use_4w()) {
-            using K4 = void (*)(const bf16_t*, long long, const bf16_t*, long long, bf16_t*, long long, int, int, int,
-                                Epi, int, int, int, int, int, float*, W4Sched);
-            // (a static table's constant initializer left the kernels' host stubs un-instantiated)
-            const K4 kern4[6] = {gemm_bf16_tn_4w<VS_EPI_BIAS, false>, gemm_bf16_tn_4w<VS_EPI_GELU, false>,
-                                        gemm_bf16_tn_4w<VS_EPI_SILU, false>, gemm_bf16_tn_4w<VS_EPI_GATE_RES, false>,
-                                        gemm_bf16_tn_4w<VS_EPI_RES, false>, gemm_bf16_tn_4w<VS_EPI_GATE_RES, true>};
-            static bool attr4 = false;
-            if (!attr4) {
-                for (const K4 f : kern4)
-                    (void)hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS + 16);
-                attr4 = true;
-            }
-            const K4 kf = kern4[(ep.mode == VS_EPI_GATE_RES && ep.hint) ? 5 : ep.mode];
-            // raster groups of 2 M-tiles for the deep-K FFN-down (K 13 824: 5.47-5.48 vs 5.54-5.57 ms at
-            // 59 280 rows), 4 elsewhere (q|k|v / FFN-up 1-1.5 % slower at 2, 5-15 % at 8-16;
-            // profiles/r6/gemm_gm_s10.log).  The split combine below reads the same ep.gm
-            if (k >= 8192) ep.gm = 2;
-            const W4Sched sc = w4_sched(sp.nmain, k / 64, (hipStream_t)stream,
-                                        vs_opt(VS_OPT_PIECE_QUEUE) ? sp.ntail * sp.ksplit : 0);
-            hipLaunchKernelGGL(kf, dim3(w4_grid(sc, sp)), dim3(256), W4_LDS + 16,
-                               (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)w, ldw, (bf16_t*)c, ldc, m,
-                               n, k, ep, tm, tn, sp.nmain, sp.ksplit, sp.piece_k, part, sc);
-            VS_CHECK_LAUNCH();
-        } else {
-        hipLaunchKernelGGL(k2 ? (wide ? gemm_bf16_tn_8p<true, true> : gemm_bf16_tn_8p<true, false>)
-                              : (wide ? gemm_bf16_tn_8p<false, true> : gemm_bf16_tn_8p<false, false>),
-                           dim3((unsigned)(sp.nmain + sp.ntail * sp.ksplit)),
-                           dim3(512), LDS8, (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)w, ldw,
-                           (bf16_t*)c, ldc, m, n, k, (const bf16_t*)a2, lda2, (const bf16_t*)w2, ldw2, k2, ep, tm, tn,
-                           sp.nmain, sp.ksplit, sp.piece_k, part);
+    if (!big) {
+        const int ntm = (m + BM - 1) / BM, ntn = (n + BN - 1) / BN;
+        const long long nwg = (long long)ntm * ntn;
+        if (nwg > 0x7fffffff) return VS_E_INVALID;
+        hipLaunchKernelGGL(gemm_bf16_tn, dim3((unsigned)nwg), dim3(NTHR), 2 * STAGE_BYTES, stream, (const bf16_t*)a,
+                           lda, (const bf16_t*)w, ldw, (bf16_t*)c, ldc, m, n, k, (const bf16_t*)a2, lda2,
+                           (const bf16_t*)w2, ldw2, k2, ep, ntm, ntn);
         VS_CHECK_LAUNCH();
-        }
-        if (sp.ntail) {
-            const long long threads = (long long)sp.ntail * BT * (BT / 4);
-            hipLaunchKernelGGL(gemm_split_combine, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
-                               (hipStream_t)stream, part, (bf16_t*)c, ldc, m, n, ep, tm, tn, sp.nmain, sp.ntail,
-                               sp.ksplit);
-            VS_CHECK_LAUNCH();
-        }
         return VS_OK;
     }
-    const int ntm = (m + BM - 1) / BM, ntn = (n + BN - 1) / BN;
-    const long long nwg = (long long)ntm * ntn;
-    if (nwg > 0x7fffffff) return VS_E_INVALID;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_bf16_tn,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES);
-        attr_set = true;
+    // the last partial round of tiles runs as K pieces + combine (split tail); whole tiles with a
+    // LoRA second phase
+    const int tm = (m + BT - 1) / BT, tn = (n + BT - 1) / BT;
+    const bool wide = epi_wide(ep, n, c, ldc);
+    const bool w4 = k2 == 0 && wide && use_4w();
+    float* part = nullptr;
+    KSplit sp = k2 ? KSplit{tm * tn, 0, 1, 0} : split_tail(tm * tn, k, 64, stream, part);
+    if (w4 && vs_opt(VS_OPT_QUEUE) && vs_opt(VS_OPT_PIECE_QUEUE) == 2 && vs_opt(VS_OPT_GEMM_SPLIT)) {
+        const KSplit held = plan_ksplit_held(tm * tn, k / 64, vs_cus_for_split(false), 64);
+        if (held.ntail > sp.ntail) {
+            float* p2 = nullptr;
+            const KSplit h = split_tail(held, stream, p2);
+            if (p2) {
+                sp = h;
+                part = p2;
+            }
+        }
     }
-    hipLaunchKernelGGL(gemm_bf16_tn, dim3((unsigned)nwg), dim3(NTHR), 2 * STAGE_BYTES,
-                       (hipStream_t)stream, (const bf16_t*)a, lda, (const bf16_t*)w, ldw,
-                       (bf16_t*)c, ldc, m, n, k, (const bf16_t*)a2, lda2, (const bf16_t*)w2, ldw2,
-                       k2, ep, ntm, ntn);
+    if (w4) {
+        // raster groups of 2 M-tiles for the deep-K FFN-down (K 13 824: 5.47-5.48 vs 5.54-5.57 ms at
+        // 59 280 rows), 4 elsewhere (q|k|v / FFN-up 1-1.5 % slower at 2, 5-15 % at 8-16;
+        // profiles/r6/gemm_gm_s10.log).  The split combine below reads the same ep.gm
+        if (k >= 8192) ep.gm = 2;
+        const W4Sched sc = w4_sched(sp.nmain, k / 64, stream, vs_opt(VS_OPT_PIECE_QUEUE) ? sp.ntail * sp.ksplit : 0);
+        hipLaunchKernelGGL(bf16_4w(mode_4w(ep)), dim3(w4_grid(sc, sp)), dim3(256), W4_LDS + 16, stream,
+                           (const bf16_t*)a, lda, (const bf16_t*)w, ldw, (bf16_t*)c, ldc, m, n, k, ep, tm, tn, sp.nmain,
+                           sp.ksplit, sp.piece_k, part, sc);
+    } else {
+        // the staggered 8-phase kernel (LoRA second phase included)
+        hipLaunchKernelGGL(k2 ? (wide ? gemm_bf16_tn_8p<true, true> : gemm_bf16_tn_8p<true, false>)
+                              : (wide ? gemm_bf16_tn_8p<false, true> : gemm_bf16_tn_8p<false, false>),
+                           dim3((unsigned)(sp.nmain + sp.ntail * sp.ksplit)), dim3(512), LDS8, stream,
+                           (const bf16_t*)a, lda, (const bf16_t*)w, ldw, (bf16_t*)c, ldc, m, n, k, (const bf16_t*)a2,
+                           lda2, (const bf16_t*)w2, ldw2, k2, ep, tm, tn, sp.nmain, sp.ksplit, sp.piece_k, part);
+    }
     VS_CHECK_LAUNCH();
-    return VS_OK;
+    return sp.ntail ? launch_combine(sp, part, c, ldc, m, n, ep, tm, tn, nullptr, nullptr, stream) : VS_OK;
 }
 
-// scale_w: the weight scale of vs_gemm_fp8_ws (null: vs_gemm_fp8, the unscaled instantiations)
+// the fp8 MFMA kernels (K-tiles of 128 fp8) without LoRA phase.  scale_w: the weight scale of
+// vs_gemm_fp8_ws (null: vs_gemm_fp8, the unscaled instantiations)
 static int gemm_fp8_impl(const void* a8, long long lda, const float* scale_a, const void* w8, long long ldw,
                          const float* scale_w, void* c, long long ldc, int m, int n, int k, int epilogue,
-                         const vs_epilogue* epi, void* stream) {
-    if (!a8 || !scale_a || !w8 || !c || m <= 0 || n <= 0 || k <= 0) return VS_E_INVALID;
-    // K % 128: the MFMA kernel's K-tile
-    if (k % 128 || n % 4 || lda < k || ldw < k || ldc < n || (lda & 15) || (ldw & 15) || (ldc & 3))
-        return VS_E_INVALID;
-    if (!aligned16(a8) || !aligned16(w8) || !aligned8(c)) return VS_E_INVALID;
+                         const vs_epilogue* epi, hipStream_t stream) {
+    if (!scale_a || !main_operands_ok(a8, lda, w8, ldw, c, ldc, m, n, k, 128, 15)) return VS_E_INVALID;
     Epi ep;
     const int rc = fill_epi(ep, epilogue, epi, m, n);
     if (rc) return rc;
-    // r4 kept hipBLASLt fp8 for the plain-bias q|k|v (2807 vs 3067 TF/s); with the XCD tile queues
-    // the 4-wave kernel runs it at 3013 vs 3068 and every fused-epilogue shape ahead of the library
-    // + its epilogue pass (FFN-up 2839 vs 2500, o-proj 2652 vs 2225: profiles/r5/
-    // gemm_fp8_queue_ab_s1.log), so every fp8 GEMM runs here (the library only in the A/B build)
-    // the fp8 MFMA kernels (K-tiles of 128 fp8)
+    set_lds_limits();
     const int tm = (m + BT - 1) / BT, tn = (n + BT - 1) / BT;
-    static bool attr8 = false;
-    if (!attr8) {
-        (void)hipFuncSetAttribute((const void*)gemm_fp8_tn_8p<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8);
-        (void)hipFuncSetAttribute((const void*)gemm_fp8_tn_8p<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8);
-        (void)hipFuncSetAttribute((const void*)gemm_fp8_tn_8p<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8);
-        attr8 = true;
-    }
-    KSplit sp = plan_ksplit(tm * tn, k / 128, vs_cus_for_split(!vs_opt(VS_OPT_GEMM_SPLIT)), 128);
+    const bool wide = epi_wide(ep, n, c, ldc);
     float* part = nullptr;
-    if (sp.ntail) {
-        part = vs_split_workspace(1, (size_t)sp.ntail * sp.ksplit * BT * BT * sizeof(float), (hipStream_t)stream);
-        if (!part) sp = KSplit{tm * tn, 0, 1, 0};
-    }
-    const bool wide = n % 8 == 0 && ldc % 8 == 0 && aligned16(c) && (!ep.bias || aligned16(ep.bias)) &&
-                      (!ep.res || (ep.ld_res % 8 == 0 && aligned16(ep.res))) &&
-                      (!ep.gate || (ep.gate_bstride % 8 == 0 && aligned16(ep.gate))) &&
-                      (!ep.hint || (ep.ld_hint % 8 == 0 && aligned16(ep.hint)));
-    if (scale_w) {
+    const KSplit sp = split_tail(tm * tn, k, 128, stream, part);
+    if (!scale_w && use_4w()) {            // the 4-wave kernel unless VS_OPT_GEMM_KERNEL 8
+        // persistent blocks fed by the XCD tile queues, as the bf16 kernel (w4_sched)
+        const W4Sched sc = w4_sched(sp.nmain, k / 128, stream);
+        hipLaunchKernelGGL(fp8_4w(wide ? mode_4w(ep) : 6), dim3(w4_grid(sc, sp)), dim3(256), F4_LDS + 16, stream,
+                           (const uint8_t*)a8, lda, scale_a, (const uint8_t*)w8, ldw, (bf16_t*)c, ldc, m, n, k, ep, tm,
+                           tn, sp.nmain, sp.ksplit, sp.piece_k, part, sc);
+    } else {
         // the weight scale runs on the 8-phase kernel whatever VS_OPT_GEMM_KERNEL says (16-B epilogue
         // when the operands allow it): the 4-wave kernel has no weight-scale instantiations
-        hipLaunchKernelGGL((wide ? gemm_fp8_tn_8p<false, true, true> : gemm_fp8_tn_8p<false, false, true>),
-                           dim3((unsigned)(sp.nmain + sp.ntail * sp.ksplit)), dim3(512), LDS8,
-                           (hipStream_t)stream, (const uint8_t*)a8, lda, scale_a, (const uint8_t*)w8, ldw, (bf16_t*)c,
-                           ldc, m, n, k, (const bf16_t*)nullptr, 0LL, (const bf16_t*)nullptr, 0LL, 0, ep, tm, tn, sp.nmain,
-                           sp.ksplit, sp.piece_k, part, scale_w);
-    } else if (use_4w()) {                 // the 4-wave kernel unless VS_OPT_GEMM_KERNEL 8
-        using KF4 = void (*)(const uint8_t*, long long, const float*, const uint8_t*, long long, bf16_t*, long long,
-                             int, int, int, Epi, int, int, int, int, int, float*, W4Sched);
-        // one instantiation per 16-B epilogue mode (index: mode, 5 = gate-residual + hint), 6: 8-B path
-        const KF4 kf4[7] = {gemm_fp8_tn_4w<true, VS_EPI_BIAS, false>, gemm_fp8_tn_4w<true, VS_EPI_GELU, false>,
-                            gemm_fp8_tn_4w<true, VS_EPI_SILU, false>, gemm_fp8_tn_4w<true, VS_EPI_GATE_RES, false>,
-                            gemm_fp8_tn_4w<true, VS_EPI_RES, false>, gemm_fp8_tn_4w<true, VS_EPI_GATE_RES, true>,
-                            gemm_fp8_tn_4w<false, VS_EPI_BIAS, false>};
-        static bool attr4 = false;
-        if (!attr4) {
-            for (const KF4 f : kf4)
-                (void)hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, F4_LDS + 16);
-            attr4 = true;
-        }
-        // persistent blocks fed by the XCD tile queues, as the bf16 kernel (w4_sched)
-        const W4Sched sc = w4_sched(sp.nmain, k / 128, (hipStream_t)stream);
-        const KF4 kf = kf4[!wide ? 6 : (ep.mode == VS_EPI_GATE_RES && ep.hint) ? 5 : ep.mode];
-        hipLaunchKernelGGL(kf, dim3(w4_grid(sc, sp)), dim3(256), F4_LDS + 16,
-                           (hipStream_t)stream, (const uint8_t*)a8, lda, scale_a, (const uint8_t*)w8, ldw, (bf16_t*)c,
-                           ldc, m, n, k, ep, tm, tn, sp.nmain, sp.ksplit, sp.piece_k, part, sc);
-    } else
-    hipLaunchKernelGGL((gemm_fp8_tn_8p<false, false>), dim3((unsigned)(sp.nmain + sp.ntail * sp.ksplit)), dim3(512), LDS8,
-                       (hipStream_t)stream, (const uint8_t*)a8, lda, scale_a, (const uint8_t*)w8, ldw, (bf16_t*)c,
-                       ldc, m, n, k, (const bf16_t*)nullptr, 0LL, (const bf16_t*)nullptr, 0LL, 0, ep, tm, tn, sp.nmain,
-                       sp.ksplit, sp.piece_k, part, (const float*)nullptr);
-    VS_CHECK_LAUNCH();
-    if (sp.ntail) {
-        const long long threads = (long long)sp.ntail * BT * (BT / 4);
-        if (scale_w)
-            hipLaunchKernelGGL(gemm_split_combine_ws, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
-                               (hipStream_t)stream, part, (bf16_t*)c, ldc, m, n, ep, tm, tn, sp.nmain, sp.ntail,
-                               sp.ksplit, scale_a, scale_w);
-        else
-        hipLaunchKernelGGL(gemm_split_combine, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,
-                           (hipStream_t)stream, part, (bf16_t*)c, ldc, m, n, ep, tm, tn, sp.nmain, sp.ntail,
-                           sp.ksplit, scale_a);
-        VS_CHECK_LAUNCH();
+        hipLaunchKernelGGL((!scale_w ? gemm_fp8_tn_8p<false, false>
+                                     : (wide ? gemm_fp8_tn_8p<false, true, true> : gemm_fp8_tn_8p<false, false, true>)),
+                           dim3((unsigned)(sp.nmain + sp.ntail * sp.ksplit)), dim3(512), LDS8, stream,
+                           (const uint8_t*)a8, lda, scale_a, (const uint8_t*)w8, ldw, (bf16_t*)c, ldc, m, n, k,
+                           (const bf16_t*)nullptr, 0LL, (const bf16_t*)nullptr, 0LL, 0, ep, tm, tn, sp.nmain, sp.ksplit,
+                           sp.piece_k, part, scale_w);
     }
-    return VS_OK;
+    VS_CHECK_LAUNCH();
+    return sp.ntail ? launch_combine(sp, part, c, ldc, m, n, ep, tm, tn, scale_a, scale_w, stream) : VS_OK;
 }
 
 extern "C" int vs_gemm_fp8(const void* a8, long long lda, const float* scale_a, const void* w8, long long ldw,
                            void* c, long long ldc, int m, int n, int k, int epilogue, const vs_epilogue* epi,
                            void* stream) {
-    return gemm_fp8_impl(a8, lda, scale_a, w8, ldw, nullptr, c, ldc, m, n, k, epilogue, epi, stream);
+    return gemm_fp8_impl(a8, lda, scale_a, w8, ldw, nullptr, c, ldc, m, n, k, epilogue, epi, (hipStream_t)stream);
 }
 
 // vs_gemm_fp8 + the un-merged LoRA term as the fp8 8-phase kernel's second K phase (its header).
@@ -2475,37 +2451,24 @@ extern "C" int vs_gemm_fp8(const void* a8, long long lda, const float* scale_a, 
 static int gemm_fp8_lora_impl(const void* a8, long long lda, const float* scale_a, const void* w8, long long ldw,
                               const float* scale_w, void* c, long long ldc, int m, int n, int k, int epilogue,
                               const vs_epilogue* epi, const void* a2, long long lda2, const void* w2, long long ldw2,
-                              int k2, void* stream) {
-    if (k2 < 0 || k2 % 64) return VS_E_INVALID;
+                              int k2, hipStream_t stream) {
+    if (k2 < 0 || k2 % BK) return VS_E_INVALID;
     if (k2 == 0) return gemm_fp8_impl(a8, lda, scale_a, w8, ldw, scale_w, c, ldc, m, n, k, epilogue, epi, stream);
-    if (!a8 || !scale_a || !w8 || !c || m <= 0 || n <= 0 || k <= 0) return VS_E_INVALID;
-    if (k % 128 || n % 4 || lda < k || ldw < k || ldc < n || (lda & 15) || (ldw & 15) || (ldc & 3))
-        return VS_E_INVALID;
-    if (!aligned16(a8) || !aligned16(w8) || !aligned8(c)) return VS_E_INVALID;
-    if (!a2 || !w2 || lda2 < k2 || ldw2 < k2 || (lda2 & 7) || (ldw2 & 7)) return VS_E_INVALID;
-    if (!aligned16(a2) || !aligned16(w2)) return VS_E_INVALID;
+    if (!scale_a || !main_operands_ok(a8, lda, w8, ldw, c, ldc, m, n, k, 128, 15)) return VS_E_INVALID;
+    if (!lora_operands_ok(a2, lda2, w2, ldw2, k2)) return VS_E_INVALID;
     Epi ep;
     const int rc = fill_epi(ep, epilogue, epi, m, n);
     if (rc) return rc;
+    set_lds_limits();
     const int tm = (m + BT - 1) / BT, tn = (n + BT - 1) / BT;
-    static bool attr = false;
-    if (!attr) {
-        for (const void* f : {(const void*)gemm_fp8_tn_8p<true, false>, (const void*)gemm_fp8_tn_8p<true, true>})
-            (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8 + 1024);
-        for (const void* f : {(const void*)gemm_fp8_tn_8p<true, false, true>, (const void*)gemm_fp8_tn_8p<true, true, true>})
-            (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8 + 2048);
-        attr = true;
-    }
-    const bool wide = n % 8 == 0 && ldc % 8 == 0 && aligned16(c) && (!ep.bias || aligned16(ep.bias)) &&
-                      (!ep.res || (ep.ld_res % 8 == 0 && aligned16(ep.res))) &&
-                      (!ep.gate || (ep.gate_bstride % 8 == 0 && aligned16(ep.gate))) &&
-                      (!ep.hint || (ep.ld_hint % 8 == 0 && aligned16(ep.hint)));
-    // (+ the second KB of parked scales with a weight scale: the column scales)
+    const bool wide = epi_wide(ep, n, c, ldc);
+    // (the parked scales past the buffers: set_lds_limits)
     hipLaunchKernelGGL((scale_w ? (wide ? gemm_fp8_tn_8p<true, true, true> : gemm_fp8_tn_8p<true, false, true>)
-                                : (wide ? gemm_fp8_tn_8p<true, true> : gemm_fp8_tn_8p<true, false>)), dim3((unsigned)(tm * tn)),
-                       dim3(512), LDS8 + (scale_w ? 2048 : 1024), (hipStream_t)stream, (const uint8_t*)a8, lda, scale_a,
-                       (const uint8_t*)w8, ldw, (bf16_t*)c, ldc, m, n, k, (const bf16_t*)a2, lda2, (const bf16_t*)w2, ldw2,
-                       k2, ep, tm, tn, tm * tn, 1, 0, (float*)nullptr, scale_w);
+                                : (wide ? gemm_fp8_tn_8p<true, true> : gemm_fp8_tn_8p<true, false>)),
+                       dim3((unsigned)(tm * tn)), dim3(512), LDS8 + (scale_w ? 2048 : 1024), stream,
+                       (const uint8_t*)a8, lda, scale_a, (const uint8_t*)w8, ldw, (bf16_t*)c, ldc, m, n, k,
+                       (const bf16_t*)a2, lda2, (const bf16_t*)w2, ldw2, k2, ep, tm, tn, tm * tn, 1, 0, (float*)nullptr,
+                       scale_w);
     VS_CHECK_LAUNCH();
     return VS_OK;
 }
@@ -2514,19 +2477,19 @@ extern "C" int vs_gemm_fp8_lora(const void* a8, long long lda, const float* scal
                                 void* c, long long ldc, int m, int n, int k, int epilogue, const vs_epilogue* epi,
                                 const void* a2, long long lda2, const void* w2, long long ldw2, int k2, void* stream) {
     return gemm_fp8_lora_impl(a8, lda, scale_a, w8, ldw, nullptr, c, ldc, m, n, k, epilogue, epi, a2, lda2, w2, ldw2, k2,
-                              stream);
+                              (hipStream_t)stream);
 }
 
 // vs_gemm_fp8 / vs_gemm_fp8_lora with the per-output-channel weight scale (include/vstyler.h):
-// C = epilogue(((A8 . W8^T) * scale_w[n]) * scale_a[m] + A2 . W2^T) on the 8-phase kernel's WS instantiations
-// (+ gemm_split_combine_ws for its split tail).
+// C = epilogue(((A8 . W8^T) * scale_w[n]) * scale_a[m] + A2 . W2^T) on the 8-phase kernel's WS
+// instantiations (the split tail's combine applies both scales in that order).
 extern "C" int vs_gemm_fp8_ws(const void* a8, long long lda, const float* scale_a, const void* w8, long long ldw,
                               const float* scale_w, void* c, long long ldc, int m, int n, int k, int epilogue,
                               const vs_epilogue* epi, const void* a2, long long lda2, const void* w2, long long ldw2,
                               int k2, void* stream) {
     if (scale_w && !aligned16(scale_w)) return VS_E_INVALID;
     return gemm_fp8_lora_impl(a8, lda, scale_a, w8, ldw, scale_w, c, ldc, m, n, k, epilogue, epi, a2, lda2, w2, ldw2, k2,
-                              stream);
+                              (hipStream_t)stream);
 }
 
 extern "C" int vs_quant_fp8_rows(const void* x, long long ldx, void* x8, long long ld8, float* scale, int rows,

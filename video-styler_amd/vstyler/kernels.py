@@ -61,11 +61,11 @@ _SPLIT_WS = {}
 
 
 def _split_ws(kind, t, nbytes=None):
-    """Bind library scratch of `kind` (0 attention split tail, 1 GEMM split tail, 2 / 3 unused since
-    r6 (the removed vendor-library route), 4 attention item flags, 5 GEMM tile and attention item
-    queues) for the current stream of t's device from the torch
-    allocator (vs_split_workspace_bind: the library never allocates).  Re-bound larger when a
-    bigger one is needed; never inside a graph capture (the library then takes its fallback)."""
+    """Bind library scratch of `kind` (0 attention split tail, 1 GEMM split tail, 4 attention item
+    flags, 5 GEMM tile and attention item queues; 2 and 3 are retired numbers no caller binds) for the
+    current stream of t's device from the torch allocator (vs_split_workspace_bind: the library never
+    allocates).  Re-bound larger when a bigger one is needed; never inside a graph capture (the
+    library then takes its fallback)."""
     stream = _stream(t)
     key = (kind, t.device.index, stream)
     have = _SPLIT_WS.get(key)
@@ -73,7 +73,7 @@ def _split_ws(kind, t, nbytes=None):
         if have is not None:
             return
         nbytes = _lib.load().vs_split_workspace_bytes(kind)
-        if nbytes <= 0:             # a kind this build does not use (2, 3)
+        if nbytes <= 0:             # a kind the library does not use
             return
     elif have is not None and have.numel() >= nbytes:
         return
@@ -150,10 +150,6 @@ def gemm(a, w, out, epilogue=VS_EPI_BIAS, bias=None, residual=None, gate=None, g
     if k2 == 0:
         _split_ws(1, a)
         _split_ws(5, a)
-        if gemm_route(M, N, K, epilogue=epilogue):   # the A/B build's library route only
-            _split_ws(2, a)
-            if epilogue in (VS_EPI_GATE_RES, VS_EPI_RES):
-                _split_ws(3, a, M * N * 2)
     _lib.check(_lib.load().vs_gemm(a.data_ptr(), lda, w.data_ptr(), ldw, out.data_ptr(), ldc, M, N, K,
                                    int(epilogue), ep, _ptr(a2), lda2, _ptr(w2), ldw2, k2, _stream(a)))
     return out
@@ -220,39 +216,23 @@ def gemm_fp8(a8, scale_a, w8, out, epilogue=VS_EPI_BIAS, bias=None, residual=Non
         raise ValueError(f"gemm_fp8 shape mismatch a8={tuple(a8.shape)} w8={tuple(w8.shape)} out={tuple(out.shape)}")
     ep = _epilogue(bias, residual, gate, gate_bstride, hint, hint_scale, alpha, rows_per_batch)
     k2 = a2.shape[1] if a2 is not None else 0
-    if scale_w is not None:
-        lda2 = ldw2 = 0
-        if k2 > 0:                                                      # whole-tile grid, no workspace
-            _, _, lda2 = _rows(a2, "a2")
-            _, _, ldw2 = _rows(w2, "w2")
-        else:
-            _split_ws(1, a8)
-            _split_ws(5, a8)
-        _lib.check(_lib.load().vs_gemm_fp8_ws(a8.data_ptr(), lda, scale_a.data_ptr(), w8.data_ptr(), ldw,
-                                              scale_w.data_ptr(), out.data_ptr(), ldc, M, N, K, int(epilogue), ep,
-                                              a2.data_ptr() if k2 else None, lda2, w2.data_ptr() if k2 else None, ldw2,
-                                              k2, _stream(a8)))
-        return out
-    if k2 > 0:                                                          # whole-tile grid, no workspace
+    lda2 = ldw2 = 0
+    if k2 > 0:                                      # whole-tile grid, no workspace
         _, _, lda2 = _rows(a2, "a2")
         _, _, ldw2 = _rows(w2, "w2")
-        _lib.check(_lib.load().vs_gemm_fp8_lora(a8.data_ptr(), lda, scale_a.data_ptr(), w8.data_ptr(), ldw,
-                                                out.data_ptr(), ldc, M, N, K, int(epilogue), ep, a2.data_ptr(), lda2,
-                                                w2.data_ptr(), ldw2, k2, _stream(a8)))
-        return out
-    _split_ws(1, a8)                                                    # split tail of the MFMA kernel
-    _split_ws(5, a8)                                                    # its tile queues
-    if gemm_route(M, N, K, epilogue=epilogue, fp8=True):                # the A/B build's library route only
-        _split_ws(2, a8)
-        if epilogue in (VS_EPI_GATE_RES, VS_EPI_RES):
-            _split_ws(3, a8, M * N * 2)
-    if a2 is not None:                                                  # an empty LoRA phase: vs_gemm_fp8 by the new entry
-        _lib.check(_lib.load().vs_gemm_fp8_lora(a8.data_ptr(), lda, scale_a.data_ptr(), w8.data_ptr(), ldw,
-                                                out.data_ptr(), ldc, M, N, K, int(epilogue), ep, None, 0, None, 0, 0,
-                                                _stream(a8)))
-        return out
-    _lib.check(_lib.load().vs_gemm_fp8(a8.data_ptr(), lda, scale_a.data_ptr(), w8.data_ptr(), ldw, out.data_ptr(),
-                                       ldc, M, N, K, int(epilogue), ep, _stream(a8)))
+    else:
+        _split_ws(1, a8)                            # split tail of the MFMA kernel
+        _split_ws(5, a8)                            # its tile queues
+    lib = _lib.load()
+    head = (a8.data_ptr(), lda, scale_a.data_ptr(), w8.data_ptr(), ldw)
+    body = (out.data_ptr(), ldc, M, N, K, int(epilogue), ep)
+    lora = (a2.data_ptr() if k2 else None, lda2, w2.data_ptr() if k2 else None, ldw2, k2)
+    if scale_w is not None:
+        _lib.check(lib.vs_gemm_fp8_ws(*head, scale_w.data_ptr(), *body, *lora, _stream(a8)))
+    elif a2 is not None:                            # (an empty LoRA phase too: vs_gemm_fp8 by this entry)
+        _lib.check(lib.vs_gemm_fp8_lora(*head, *body, *lora, _stream(a8)))
+    else:
+        _lib.check(lib.vs_gemm_fp8(*head, *body, _stream(a8)))
     return out
 
 
@@ -322,8 +302,9 @@ def layernorm_modulate_fp8(x, x8, qscale, eps=1e-6, shift=None, scale=None, mod_
 def residual_layernorm(y, x, out, eps=1e-6, epilogue=VS_EPI_GATE_RES, gate=None, gate_bstride=0, gate_rows=0,
                        alpha=1.0, hint=None, hint_scale=1.0, shift=None, scale=None, mod_bstride=0,
                        rows_per_batch=0, weight=None, bias=None):
-    """x = epilogue(y, x) (gate-residual / residual of a staged projection y), then
-    out = layernorm_modulate(x) -- one pass (vs_residual_layernorm)."""
+    """x = epilogue(y, x) (gate-residual / residual of a bf16 projection y the caller holds), then
+    out = layernorm_modulate(x) -- one pass over the rows (vs_residual_layernorm).  A standalone fused
+    row op of the ABI: the model does not call it, every GEMM of the model fuses its own epilogue."""
     M, D, ldy = _rows(y, "y")
     Mx, Dx, ldx = _rows(x, "x")
     Mo, Do, ldo = _rows(out, "out")
@@ -334,17 +315,6 @@ def residual_layernorm(y, x, out, eps=1e-6, epilogue=VS_EPI_GATE_RES, gate=None,
                                                  int(epilogue), ep, int(rows_per_batch), _ptr(shift), _ptr(scale),
                                                  int(mod_bstride), _ptr(weight), _ptr(bias), float(eps), _stream(x)))
     return out
-
-
-def gemm_route(M, N, K, epilogue=None, fp8=False):
-    """True if vs_gemm (vs_gemm_fp8 with fp8=True) runs an (M, N, K) GEMM without LoRA phase and with
-    `epilogue` as a staged product + a separate epilogue pass (vs_gemm_route / vs_gemm_route_epi):
-    never in the product library (every GEMM fuses its epilogue), the vendor-library route of the
-    A/B build (make ab)."""
-    if epilogue is None and not fp8:
-        return _lib.load().vs_gemm_route(int(M), int(N), int(K)) == 1
-    ep = VS_EPI_BIAS if epilogue is None else int(epilogue)
-    return _lib.load().vs_gemm_route_epi(int(M), int(N), int(K), ep, 1 if fp8 else 0) == 1
 
 
 def rmsnorm_rope(x, weight, eps=1e-6, rope=None, grid=(1, 1, 1), rows_per_batch=0, token_offset=0, head_dim=128):

@@ -101,19 +101,6 @@ def linear(lin, x, out, ws, **epi):
     return K.gemm(x, lin.weight, out, bias=lin.bias, a2=a2, w2=w2, **epi)
 
 
-def _fusable_lt(lin, M, epilogue):
-    """True when `lin` on M rows with the residual `epilogue` would run as a staged product + a separate
-    epilogue pass (vs_gemm_route_epi != 0: the vendor-library route of the A/B build only; the
-    product library fuses every epilogue), i.e. when that pass could fuse with the LayerNorm that
-    follows (vs_residual_layernorm) with the same rounding points.  Otherwise the residual epilogue is
-    fused into the GEMM and the LayerNorm runs alone.  A hot-loaded LoRA keeps the MFMA kernel's fused
-    epilogue.  Host option fuse_res_ln=0 disables."""
-    if getattr(lin, "lora_A", None) is not None or not host_option("fuse_res_ln"):
-        return False
-    fp8 = getattr(lin, "weight_fp8", None) is not None
-    return K.gemm_route(M, lin.out_features, lin.in_features, epilogue=epilogue, fp8=fp8)
-
-
 FP8_WEIGHT_SCALE_MODES = ("channel", "tensor")
 
 
@@ -396,12 +383,6 @@ class RunCtx:
         self.ctx, self.ctx_len, self.ws = ctx, ctx_len, ws
         self.sp = sp                    # vstyler.usp.UlyssesGroup or None
         self.token_offset = token_offset
-        # set by a block whose FFN-down residual was fused with the next consumer's LayerNorm
-        # (DiTBlock.forward nxt=): the ws buffer holding the next block's modulation, whose h
-        # buffers then already hold its modulated LN1
-        self.pre_mod = None
-        self.mod_slot = 0
-        self.t_emb = None               # the time embedding t [B, D] (the head's modulation input)
 
 
 class DiTBlock(nn.Module):
@@ -416,12 +397,11 @@ class DiTBlock(nn.Module):
         self.ffn = Sequential3(Linear(dim, ffn_dim, device=device), Linear(ffn_dim, dim, device=device))
         self.modulation = _param(1, 6, dim, device=device)
 
-    def forward(self, x, t_mod, rc, hint=None, hint_scale=1.0, only_batch=None, nxt=None, shared_prefix=False):
+    def forward(self, x, t_mod, rc, hint=None, hint_scale=1.0, only_batch=None, shared_prefix=False):
         """x: [B*S, D] updated in place.  t_mod: [B, 6, D].  hint: [B*S, D] added after the block.
         only_batch: run the block for that CFG sample only (skip-layer guidance leaves the others'
-        rows untouched).  nxt: the module that consumes x next (a DiTBlock or the Head) when it runs
-        on all rows: the FFN-down gate-residual (+ VACE hint) is then fused with its modulated
-        LayerNorm (vs_residual_layernorm, one pass over the rows instead of two).
+        rows untouched).  Every GEMM fuses its epilogue (residual, gate, hint); each LayerNorm is a pass
+        of its own.
 
         Four phases per micro-batch: (1) LN1 + q/k/v + QK-RMSNorm/RoPE, (2) self-attention,
         (3) o-proj (gated residual) + LN3, (4) cross-attention, FFN (gated residual + VACE hint).
@@ -440,17 +420,13 @@ class DiTBlock(nn.Module):
         query too comes from sample 0's rows alone: the same per-row arithmetic, bit-identical
         (tests/test_model_gpu.py), half the self-attention of those blocks."""
         B, S, D, ws = rc.batch, rc.seq, self.dim, rc.ws
-        if rc.pre_mod is not None:          # the previous block already ran this one's LN1
-            mod, ln1_done = rc.pre_mod, True
-            rc.pre_mod = None
-        else:
-            rc.mod_slot ^= 1
-            mod, ln1_done = ws.get(f"mod{rc.mod_slot}", (B, 6, D)), False
-            K.mod_add(self.modulation.view(6, D), t_mod, mod, 6 * D, D)   # :218-219
+        # one buffer for every block: mod_add and every kernel that reads mod (the LayerNorms, the
+        # gated GEMM epilogues) are enqueued on the current stream; side streams carry collectives only
+        mod = ws.get("mod", (B, 6, D))
+        K.mod_add(self.modulation.view(6, D), t_mod, mod, 6 * D, D)   # :218-219
         sp = rc.sp
         shared = shared_prefix and B > 1 and only_batch is None and bool(host_option("cfg_prefix"))
         if only_batch is not None:
-            assert not ln1_done, "a skip-layer-guidance block cannot start from a fused LN1"
             parts = [self._part(x, mod, rc, only_batch, 1, hint, f".{only_batch}")]
         elif shared:
             parts = [self._part(x, mod, rc, 0, 1, hint, ".0")]
@@ -458,24 +434,9 @@ class DiTBlock(nn.Module):
             parts = [self._part(x, mod, rc, b, 1, hint, f".{b}") for b in range(B)]
         else:
             parts = [self._part(x, mod, rc, 0, B, hint, "")]
-        for p in parts:
-            p["ln1_done"] = ln1_done
         # phase 4 on all rows at once (the overlapped SP micro-batches, the shared prefix)
         tail = self._part(x, mod, rc, 0, B, hint, "") if shared or (len(parts) > 1 and
                                                                     host_option("sp_merge_ffn")) else None
-        # the fused FFN-down epilogue needs the consumer's modulation first (its own mod buffer)
-        fuse = None
-        if nxt is not None and only_batch is None and \
-                _fusable_lt(self.ffn[2], (tail or parts[0])["M"], K.VS_EPI_GATE_RES) and \
-                host_option("fuse_ffn_ln"):
-            if isinstance(nxt, DiTBlock):
-                nslot = rc.mod_slot ^ 1
-                nmod = ws.get(f"mod{nslot}", (B, 6, D))
-                K.mod_add(nxt.modulation.view(6, D), t_mod, nmod, 6 * D, D)
-                fuse = dict(shift=nmod[:, 0], scale=nmod[:, 1], bstride=6 * D, mod=nmod, slot=nslot)
-            elif isinstance(nxt, Head) and (len(parts) == 1 or tail is not None):
-                hm = nxt.modulation_for(rc.t_emb, rc)
-                fuse = dict(shift=hm[:, 0], scale=hm[:, 1], bstride=2 * D, mod=None)
         for p in parts:
             self._phase_qkv(p, rc)
         for p in parts:
@@ -483,25 +444,19 @@ class DiTBlock(nn.Module):
         for p in parts:
             self._phase_o(p, rc, direct=tail is None)
             if tail is None:
-                self._phase_cross_ffn(p, rc, hint_scale, fuse)
+                self._phase_cross_ffn(p, rc, hint_scale)
         if shared:                          # sample 0's phase 1-3 results are every sample's: x, and the
             xs = x.view(B, S, D)            # cross-attention query (from sample 0's LN3 rows in h)
             xs[1:].copy_(xs[0:1].expand(B - 1, S, D))
             tail["shared_q"] = True
         if tail is not None:
-            self._phase_cross_ffn(tail, rc, hint_scale, fuse)
-        if fuse is not None:
-            if fuse["mod"] is not None:
-                rc.pre_mod = fuse["mod"]
-                rc.mod_slot = fuse["slot"]
-            else:
-                rc.head_ln_done = True
+            self._phase_cross_ffn(tail, rc, hint_scale)
         return x
 
     def _part(self, x, mod, rc, b0, nb, hint, tag):
         S, D, L, ws = rc.seq, self.dim, rc.ctx_len, rc.ws
         r0, M = b0 * S, nb * S
-        p = dict(nb=nb, M=M, b0=b0, x=x[r0:r0 + M], mod=mod[b0:b0 + nb], ctx=rc.ctx[b0 * L:(b0 + nb) * L],
+        p = dict(nb=nb, M=M, x=x[r0:r0 + M], mod=mod[b0:b0 + nb], ctx=rc.ctx[b0 * L:(b0 + nb) * L],
                  hint=None if hint is None else hint[r0:r0 + M], tag=tag)
         for n in ("h", "q", "k", "v", "o"):     # row slices of the all-samples buffers
             p[n] = ws.get(n, (rc.batch * S, D))[r0:r0 + M]
@@ -512,9 +467,8 @@ class DiTBlock(nn.Module):
         S, D, eps, ws = rc.seq, self.dim, self.eps, rc.ws
         mod, h, q, k, v = p["mod"], p["h"], p["q"], p["k"], p["v"]
         sa = self.self_attn
-        if not p["ln1_done"]:
-            h = ln_into(p["x"], h, ws, sa, eps, shift=mod[:, 0], scale=mod[:, 1], mod_bstride=6 * D,
-                        rows_per_batch=S)
+        h = ln_into(p["x"], h, ws, sa, eps, shift=mod[:, 0], scale=mod[:, 1], mod_bstride=6 * D,
+                    rows_per_batch=S)
         qkv = fused_linear(sa, h, ws, "qkv" + p["tag"])
         if qkv is not None:            # one GEMM; q/k/v are column slices of [M, 3D]
             q, k, v = p["q"], p["k"], p["v"] = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
@@ -541,24 +495,16 @@ class DiTBlock(nn.Module):
         """direct: this part's cross-attention runs next (its LN3 may go straight into an fp8 cross-q's
         quantised input); False: the merged SP tail reads the bf16 LN3 rows of every part."""
         S, D, eps, ws = rc.seq, self.dim, self.eps, rc.ws
-        x, mod, h, o, M = p["x"], p["mod"], p["h"], p["o"], p["M"]
+        x, mod, h, o = p["x"], p["mod"], p["h"], p["o"]
         if rc.sp is not None:
             rc.sp.finish(p["xchg"], o)
-        sa = self.self_attn
-        if _fusable_lt(sa.o, M, K.VS_EPI_GATE_RES):
-            # hipBLASLt route: bf16(o Wo^T + b) staged, then gate-residual + LN3 in one pass
-            y = ws.get("res_y" + p["tag"], (M, D))
-            linear(sa.o, o, y, ws)
-            K.residual_layernorm(y, x, h, eps, epilogue=K.VS_EPI_GATE_RES, gate=mod[:, 2], gate_bstride=6 * D,
-                                 gate_rows=S, weight=self.norm3.weight, bias=self.norm3.bias)
-        else:
-            linear(sa.o, o, x, ws, epilogue=K.VS_EPI_GATE_RES, residual=x, gate=mod[:, 2],
-                   gate_bstride=6 * D, rows_per_batch=S)
-            # --- cross-attention (wan_video_dit.py:227, :171-186)
-            p["h3"] = ln_into(x, h, ws, self.cross_attn.q if direct else None, eps, weight=self.norm3.weight,
-                              bias=self.norm3.bias)
+        linear(self.self_attn.o, o, x, ws, epilogue=K.VS_EPI_GATE_RES, residual=x, gate=mod[:, 2],
+               gate_bstride=6 * D, rows_per_batch=S)
+        # --- cross-attention (wan_video_dit.py:227, :171-186)
+        p["h3"] = ln_into(x, h, ws, self.cross_attn.q if direct else None, eps, weight=self.norm3.weight,
+                          bias=self.norm3.bias)
 
-    def _phase_cross_ffn(self, p, rc, hint_scale, fuse=None):
+    def _phase_cross_ffn(self, p, rc, hint_scale):
         S, D, eps, ws = rc.seq, self.dim, self.eps, rc.ws
         x, mod, h, q, o, nb, M = p["x"], p["mod"], p["h"], p["q"], p["o"], p["nb"], p["M"]
         ca = self.cross_attn
@@ -579,31 +525,14 @@ class DiTBlock(nn.Module):
             linear(ca.v, p["ctx"], vc, ws)
         K.rmsnorm_rope(kc, ca.norm_k.weight, eps)
         K.attention(q, kc, vc, o, self.num_heads, nb)
-        if _fusable_lt(ca.o, M, K.VS_EPI_RES):
-            y = ws.get("res_y" + p["tag"], (M, D))
-            linear(ca.o, o, y, ws)
-            K.residual_layernorm(y, x, h, eps, epilogue=K.VS_EPI_RES, alpha=1.0, shift=mod[:, 3], scale=mod[:, 4],
-                                 mod_bstride=6 * D, rows_per_batch=S)
-        else:
-            linear(ca.o, o, x, ws, epilogue=K.VS_EPI_RES, residual=x)
-            # --- FFN (wan_video_dit.py:228-229) + VACE hint (wan_video_new.py:1450)
-            h = ln_into(x, h, ws, self.ffn[0], eps, shift=mod[:, 3], scale=mod[:, 4], mod_bstride=6 * D,
-                        rows_per_batch=S)
+        linear(ca.o, o, x, ws, epilogue=K.VS_EPI_RES, residual=x)
+        # --- FFN (wan_video_dit.py:228-229) + VACE hint (wan_video_new.py:1450)
+        h = ln_into(x, h, ws, self.ffn[0], eps, shift=mod[:, 3], scale=mod[:, 4], mod_bstride=6 * D,
+                    rows_per_batch=S)
         f = ws.get("f" + p["tag"], (M, self.ffn_dim))
         linear(self.ffn[0], h, f, ws, epilogue=K.VS_EPI_GELU)
-        if fuse is not None:
-            # bf16(f W2^T + b) staged, then x += gate * y (+ hint) and the next consumer's modulated
-            # LayerNorm of the new x into h (its LN1 / the head's norm) in one pass
-            y = ws.get("res_y" + p["tag"], (M, D))
-            linear(self.ffn[2], f, y, ws)
-            b0, nb = p["b0"], p["nb"]
-            K.residual_layernorm(y, x, h, eps, epilogue=K.VS_EPI_GATE_RES, gate=mod[:, 5], gate_bstride=6 * D,
-                                 gate_rows=S, hint=p["hint"], hint_scale=hint_scale,
-                                 shift=fuse["shift"][b0:b0 + nb], scale=fuse["scale"][b0:b0 + nb],
-                                 mod_bstride=fuse["bstride"], rows_per_batch=S)
-        else:
-            linear(self.ffn[2], f, x, ws, epilogue=K.VS_EPI_GATE_RES, residual=x,
-                   gate=mod[:, 5], gate_bstride=6 * D, rows_per_batch=S, hint=p["hint"], hint_scale=hint_scale)
+        linear(self.ffn[2], f, x, ws, epilogue=K.VS_EPI_GATE_RES, residual=x,
+               gate=mod[:, 5], gate_bstride=6 * D, rows_per_batch=S, hint=p["hint"], hint_scale=hint_scale)
 
 
 class Head(nn.Module):
@@ -615,22 +544,13 @@ class Head(nn.Module):
         self.head = Linear(dim, out_dim * math.prod(patch_size), device=device)
         self.modulation = _param(1, 2, dim, device=device)
 
-    def modulation_for(self, t, rc):
-        """(modulation + t) [B, 2, D] (:267, per-batch t row) in its workspace buffer."""
-        B, D = rc.batch, self.dim
-        hm = rc.ws.get("head_mod", (B, 2, D))
-        K.mod_add(self.modulation.view(2, D), t, hm, D, 0)
-        return hm
-
     def forward(self, x, t, rc):
         B, S, D, ws = rc.batch, rc.seq, self.dim, rc.ws
         h = ws.get("h", (B * S, D))
-        if getattr(rc, "head_ln_done", False):     # fused into the last block's FFN-down epilogue
-            rc.head_ln_done = False
-        else:
-            hm = self.modulation_for(t, rc)
-            K.layernorm_modulate(x, h, self.eps, shift=hm[:, 0], scale=hm[:, 1], mod_bstride=2 * D,
-                                 rows_per_batch=S)
+        hm = ws.get("head_mod", (B, 2, D))
+        K.mod_add(self.modulation.view(2, D), t, hm, D, 0)      # :267, per-batch t row
+        K.layernorm_modulate(x, h, self.eps, shift=hm[:, 0], scale=hm[:, 1], mod_bstride=2 * D,
+                             rows_per_batch=S)
         out = ws.get("head_out", (B * S, self.head.out_features))
         K.gemm(h, self.head.weight, out, bias=self.head.bias)
         return out
@@ -738,7 +658,6 @@ class VaceWanModel(nn.Module):
         M = rc.batch * rc.seq
         c = vace_cols_out
         hints = []
-        nb = len(self.vace_blocks)
         # with a shared prefix block 0 reads sample 0's rows of c0 alone and overwrites the others
         # after its self-attention half, so before_proj runs on those rows only
         rows = rc.seq if shared_prefix and rc.batch > 1 and host_option("cfg_prefix") else M
@@ -747,8 +666,7 @@ class VaceWanModel(nn.Module):
                 c0 = ws.get("vace_c", (M, D))
                 linear(blk.before_proj, c[:rows], c0[:rows], ws, epilogue=K.VS_EPI_RES, residual=x[:rows])
                 c = c0
-            blk(c, t_mod, rc, nxt=self.vace_blocks[n + 1] if n + 1 < nb else None,
-                shared_prefix=shared_prefix and n == 0)
+            blk(c, t_mod, rc, shared_prefix=shared_prefix and n == 0)
             hint = ws.get(f"vace_hint{n}", (M, D))
             linear(blk.after_proj, c, hint, ws)
             hints.append(hint)

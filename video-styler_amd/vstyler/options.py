@@ -15,8 +15,6 @@ option), read once when the package is imported.
   sp_merge_ffn    1      Ulysses overlap: phase 4 (cross-attention + FFN) over both samples' rows at once
   cfg_parallel    0      "0" Ulysses over all ranks, "1" CFG parallelism x Ulysses, "auto" CFG
                          parallelism at world size 2 only (usp.get_default_group)
-  fuse_res_ln     1      the residual + LayerNorm fused into the producing GEMM's consumer (models)
-  fuse_ffn_ln     1      the next block's LN1 fused after the FFN-down epilogue (models)
   ws_poison       0      Workspace fills every fresh buffer with NaN (debugging stale reads)
   graph           1      hipGraph replay of the denoising step (pipeline.WanVideoPipeline.denoise)
   cfg_prefix      1      the first DiT block's and the first VACE block's phases 1-3 (LN1, q|k|v,
@@ -25,8 +23,7 @@ option), read once when the package is imported.
 """
 HOST_DEFAULTS = {
     "sp_overlap": 1, "sp_comm": "torch", "sp_comm_stream": "side", "sp_graph": 0, "sp_rows": 1,
-    "sp_merge_ffn": 1, "cfg_parallel": "0", "fuse_res_ln": 1, "fuse_ffn_ln": 1, "ws_poison": 0, "graph": 1,
-    "cfg_prefix": 1,
+    "sp_merge_ffn": 1, "cfg_parallel": "0", "ws_poison": 0, "graph": 1, "cfg_prefix": 1,
 }
 _CHOICES = {"sp_comm": ("torch", "native"), "sp_comm_stream": ("side", "caller"),
             "cfg_parallel": ("0", "1", "auto")}

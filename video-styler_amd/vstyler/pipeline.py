@@ -189,24 +189,15 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     else:
         if tea_cache is not None:
             tea_cache.begin(x)
-        rc.t_emb = t
         hints = vace(x, vace_x, t_mod, rc, shared_prefix=shared_vace) if vace_x is not None else None
         vmap = vace.vace_layers_mapping if hints is not None else {}
-        nblk = len(dit.blocks)
-        # a batch-1 forward of CFG sample 1 (CFG-parallel rank) skips the slg blocks outright
-        slg_here = B > 1 or cfg_sample == 1
         for i, blk in enumerate(dit.blocks):
+            # a batch-1 forward of CFG sample 1 (CFG-parallel rank) skips the slg blocks outright
             if B == 1 and cfg_sample == 1 and i in slg_blocks:
                 continue
             hint = hints[vmap[i]] if i in vmap else None
             skip = B > 1 and i in slg_blocks
-            # the next consumer of x, whose LayerNorm this block's FFN-down epilogue can take over
-            # (not a skip-layer-guidance block, which runs on one sample's rows only or not at all)
-            if i + 1 < nblk:
-                nxt = None if (slg_here and i + 1 in slg_blocks) else dit.blocks[i + 1]
-            else:
-                nxt = None if tea_cache is not None else dit.head
-            blk(x, t_mod, rc, hint=hint, hint_scale=float(vace_scale), only_batch=0 if skip else None, nxt=nxt,
+            blk(x, t_mod, rc, hint=hint, hint_scale=float(vace_scale), only_batch=0 if skip else None,
                 shared_prefix=shared and i == 0)
         if tea_cache is not None:
             tea_cache.store(x)                                  # :1455-1456

@@ -47,6 +47,8 @@ __device__ __forceinline__ void nc_list_item(int* ws, int cap, int gi) {
     if (atomicExch(ws + 2 + gi, 1) == 0) ws[2 + cap + atomicAdd(ws, 1)] = gi;
 }
 constexpr int MODE_CHK = 0, MODE_NC = 1, MODE_REDO = 2;
+// MODE_ADD: the checked kernel with O += its result (vs_attn_fwd_add, include/vstyler_image.h)
+constexpr int MODE_ADD = 3;
 
 // attn_fwd_w4 launch (attention_w4.hip): grid blocks of 256 threads, 128 KB of dynamic LDS
 hipError_t attn_w4_launch(const AttnArgs& args, bool rebase, unsigned grid, hipStream_t stream);

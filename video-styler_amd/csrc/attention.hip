@@ -23,6 +23,7 @@
 //    cross-attention, whose 512 keys are only 8 tiles per item).
 #include "common.h"
 #include "attention.h"
+#include "../../include/vstyler_image.h"
 #include <algorithm>
 #include <set>
 
@@ -108,6 +109,17 @@ __device__ __forceinline__ f32x16_t mfma16g(bf16x8_t a, bf16x8_t b, f32x16_t c, 
 
 #define ATTN_STAMP(slot) do {} while (0)
 
+// MODE_ADD's O store: the 8 bf16 at p become bf16(old + new), new being the bf16 values the plain
+// store would have written (vs_axpy's arithmetic at scale 1: one fp32 add, one rounding)
+__device__ __forceinline__ void add_store(bf16_t* p, u32x4_t w) {
+    u32x4_t* dst = reinterpret_cast<u32x4_t*>(p);
+    const u32x4_t old = *dst;
+    u32x4_t r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = pack2(bflo(old[j]) + bflo(w[j]), bfhi(old[j]) + bfhi(w[j]));
+    *dst = r;
+}
+
 
 template <bool REBASE, bool M16, int MODE>
 __global__ __launch_bounds__(NTHR) void attn_fwd_d128(const AttnArgs args) {
@@ -120,6 +132,8 @@ __global__ __launch_bounds__(NTHR) void attn_fwd_d128(const AttnArgs args) {
     // NC: optimistic softmax (comment at NC_LMIN); M16 only
     // REDO: the checked kernel over the items the NC launch listed (grid-strided over the list)
     constexpr bool NC = M16 && MODE == MODE_NC, REDO = MODE == MODE_REDO;
+    // ADD: the checked kernel whose O store is o = bf16(o + bf16(result)) (vs_attn_fwd_add)
+    constexpr bool ADD = MODE == MODE_ADD;
     // LDS images: M32 pads the rows (K 272 B, V 320 B); M16 (v_mfma_f32_16x16x32_bf16, see mfma16
     // below) stores K rows unpadded with the 16-B chunk XOR-swizzled by (row & 15) and pads V rows
     // to 288 B, so both of its read patterns are bank-conflict free
@@ -798,6 +812,9 @@ __global__ __launch_bounds__(NTHR) void attn_fwd_d128(const AttnArgs args) {
             nc_flag(g0 + (tj - 1) * gstride);      // the finished item's row sums
             bf16_t* op = ob_prev + (long long)q0_prev * ldo;
             out_chunks([&](int cidx, u32x4_t w) __attribute__((always_inline)) {
+                if constexpr (ADD) {
+                    if (out_row_ok(q0_prev, cidx)) add_store(op + ooff(cidx), w);
+                } else
                 if (out_row_ok(q0_prev, cidx)) *reinterpret_cast<u32x4_t*>(op + ooff(cidx)) = w;
             });
             // the new item starts from O = 0, l = 0
@@ -888,6 +905,9 @@ __global__ __launch_bounds__(NTHR) void attn_fwd_d128(const AttnArgs args) {
         nc_flag(g0 + (n_items - 1) * gstride);     // (tj ran past the last item)
         bf16_t* op = ob_cur + (long long)q0 * ldo;
         out_chunks([&](int cidx, u32x4_t w) __attribute__((always_inline)) {
+            if constexpr (ADD) {
+                if (out_row_ok(q0, cidx)) add_store(op + ooff(cidx), w);
+            } else
             if (out_row_ok(q0, cidx)) *reinterpret_cast<u32x4_t*>(op + ooff(cidx)) = w;
         });
     }
@@ -1083,6 +1103,60 @@ extern "C" int vs_attn_fwd(const void* q, const void* k, const void* v, void* o,
         r.nmain = r.npers = (int)rgrid;
         if (!launch(pick(MODE_REDO), rgrid, r)) return VS_E_LAUNCH;
     }
+    return VS_OK;
+}
+
+// vs_attn_fwd_add (include/vstyler_image.h): o += attention, on the checked 8-wave kernel alone -- no
+// optimistic pass (a redone item would add twice) and no split tail (its combine stores O; items of
+// at most 31 key tiles are never split: plan_split needs 32).  The grid is vs_attn_fwd's: whole items,
+// walked persistently from 8 key tiles up; an item's arithmetic does not depend on the walk.
+extern "C" int vs_attn_fwd_add(const void* q, const void* k, const void* v, void* o, int batch, int sq,
+                               int skv, int heads, int head_dim, long long ldq, long long ldk,
+                               long long ldv, long long ldo, long long bsq, long long bsk,
+                               long long bsv, long long bso, float scale, void* stream) {
+    if (!q || !k || !v || !o || batch <= 0 || sq <= 0 || skv <= 0 || heads <= 0) return VS_E_INVALID;
+    if (head_dim != HD) return VS_E_UNSUPPORTED;
+    if (ldq < (long long)heads * HD || ldk < (long long)heads * HD || ldv < (long long)heads * HD ||
+        ldo < (long long)heads * HD)
+        return VS_E_INVALID;
+    if ((ldq | ldk | ldv | ldo | bsq | bsk | bsv | bso) & 7) return VS_E_INVALID;
+    if (bsq < 0 || bsk < 0 || bsv < 0 || bso < 0) return VS_E_INVALID;
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o)) return VS_E_INVALID;
+    if (skv > 31 * BKV) return VS_E_UNSUPPORTED;
+    if ((long long)BKV * ldk * 2 >= (1LL << 31) || (long long)BKV * ldv * 2 >= (1LL << 31)) return VS_E_UNSUPPORTED;
+    // o is read and written: it must lie apart from q / k / v
+    auto span = [&](const void* p, long long bs, long long ld, int rows) {
+        const char* b = (const char*)p;
+        return std::make_pair(b, b + 2 * ((long long)(batch - 1) * bs + (long long)(rows - 1) * ld + heads * HD));
+    };
+    const auto so = span(o, bso, ldo, sq);
+    for (const auto& s : {span(q, bsq, ldq, sq), span(k, bsk, ldk, skv), span(v, bsv, ldv, skv)})
+        if (so.first < s.second && s.first < so.second) return VS_E_INVALID;
+    const int nqb = (sq + BQ - 1) / BQ;
+    const long long nwg = (long long)nqb * heads * batch;
+    if (nwg > 0x7fffffff) return VS_E_INVALID;
+    const bool m16 = vs_opt(VS_OPT_ATTN_MFMA) == 16;
+    const bool rebase = (long long)skv * ldk * 2 >= (1LL << 31) || (long long)skv * ldv * 2 >= (1LL << 31);
+    const int nkv = (skv + BKV - 1) / BKV;
+    const int ncu = vs_cus_for_split(false);
+    const bool span_ok = (long long)sq * ldq * 2 < (1LL << 32) && (long long)sq * ldo * 2 < (1LL << 32);
+    const int npers = (vs_opt(VS_OPT_ATTN_PERSIST) && span_ok && ncu > 0 && nkv >= PERSIST_MIN_TILES && nwg > ncu)
+                          ? ncu : (int)nwg;
+    AttnArgs args{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, bsq, bsk, bsv, bso,
+                  ldq, ldk, ldv, ldo, nullptr, nullptr, scale * 1.4426950408889634f, sq, skv, heads, nqb, (int)nwg,
+                  npers, 1, 0, 0, nullptr};
+    constexpr int A = MODE_ADD;
+    void (*kern)(AttnArgs) = m16 ? (rebase ? attn_fwd_d128<true, true, A> : attn_fwd_d128<false, true, A>)
+                                 : (rebase ? attn_fwd_d128<true, false, A> : attn_fwd_d128<false, false, A>);
+    {
+        static std::mutex mu;
+        static std::set<const void*> attr_done;
+        std::lock_guard<std::mutex> lock(mu);
+        if (attr_done.insert((const void*)kern).second)
+            (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)npers), dim3(NTHR), LDS_BYTES, (hipStream_t)stream, args);
+    VS_CHECK_LAUNCH();
     return VS_OK;
 }
 

@@ -2,6 +2,7 @@
 // All loads/stores are 16-B vectorised (8 bf16 per lane); normalisations keep the row in
 // registers between the reduction and the write (one HBM read + one write per element).
 #include "common.h"
+#include "../../include/vstyler_image.h"
 
 namespace {
 
@@ -734,6 +735,91 @@ extern "C" int vs_axpy(void* x, const void* y, float scale, long long n, void* s
     const long long n8 = n / 8;
     hipLaunchKernelGGL(axpy_kernel, dim3(nblk(n8, 256)), dim3(256), 0, (hipStream_t)stream,
                        (bf16_t*)x, (const bf16_t*)y, scale, n8);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+
+// ---- image conditioning (include/vstyler_image.h) ------------------------------------------------
+namespace {
+
+// im2col of Conv3d(cx + cy, D, (1,2,2)) over cat([x, y], 1): one thread per (token, 8 columns = two
+// channels' 2x2 patches), one 16-B store; channels past cx + cy (the row's K padding) store zeros
+__global__ void patchify2_kernel(const bf16_t* __restrict__ x, long long x_bs, int cx, const bf16_t* __restrict__ y,
+                                 long long y_bs, int cy, bf16_t* __restrict__ tok, long long ld, int T, int H,
+                                 int W, long long total) {
+    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int h2 = H >> 1, w2 = W >> 1, nch = (int)(ld >> 3);
+    const int ch = (int)(i % nch);
+    const long long t = i / nch;               // global token (b, f, hh, ww)
+    const int ww = (int)(t % w2);
+    const int hh = (int)((t / w2) % h2);
+    const int f = (int)((t / ((long long)w2 * h2)) % T);
+    const long long b = t / ((long long)w2 * h2 * T);
+    u32x4_t o = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int c = 2 * ch + e;
+        if (c >= cx + cy) break;
+        const bf16_t* plane = c < cx ? x + b * x_bs + (long long)c * T * H * W
+                                     : y + b * y_bs + (long long)(c - cx) * T * H * W;
+        const bf16_t* src = plane + ((long long)f * H + 2 * hh) * W + 2 * ww;
+        o[2 * e] = *reinterpret_cast<const uint32_t*>(src);
+        o[2 * e + 1] = *reinterpret_cast<const uint32_t*>(src + W);
+    }
+    *reinterpret_cast<u32x4_t*>(tok + t * ld + 8 * ch) = o;
+}
+
+// bf16 bits of a double, round-to-nearest-even in one step (no intermediate fp32 rounding, no
+// dependence on the fp32 denormal mode): below the smallest normal the value is a multiple of 2^-133
+__device__ __forceinline__ uint32_t d2bf(double d) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, d);
+    const uint32_t sign = (uint32_t)(u >> 48) & 0x8000u;
+    const double a = fabs(d);
+    if (!(a < INFINITY)) return a == INFINITY ? (sign | 0x7F80u) : 0x7FC0u;
+    if (a < 0x1p-126) return sign | (uint32_t)rint(a * 0x1p133);      // 0 .. 0x80 (the carry is exact)
+    const uint64_t m = u & 0x7FFFFFFFFFFFFFFFull;
+    const uint64_t r = (m + ((1ull << 44) - 1) + ((m >> 45) & 1)) >> 45;   // [exponent 11 | mantissa 7]
+    const uint64_t v = r - ((uint64_t)(1023 - 127) << 7);
+    return sign | (v >= 0x7F80u ? 0x7F80u : (uint32_t)v);
+}
+
+// gelu(v) = 0.5 v (1 + erf(v / sqrt 2)) = 0.5 v erfc(-v / sqrt 2): the erfc form has no cancellation
+// on the negative side; evaluated in fp64 (a [257, D] tensor once per forward: not a hot loop)
+__global__ __launch_bounds__(256) void gelu_erf_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ out,
+                                                       long long n) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double v = (double)bf2f(x[i]);
+    out[i] = (bf16_t)d2bf(0.5 * v * erfc(-v * 0.70710678118654752440));
+}
+
+}  // namespace
+
+extern "C" int vs_patchify2(const void* x, long long x_bs, int cx, const void* y, long long y_bs, int cy,
+                            void* tokens, long long ld, int batch, int frames, int height, int width, void* stream) {
+    if (!x || !tokens || (cy > 0 && !y) || batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || cx < 1 || cy < 0)
+        return VS_E_INVALID;
+    if (height % 2 || width % 2 || ld % 8 || ld < 4LL * ((long long)cx + cy) || x_bs < 0 || y_bs < 0 ||
+        (x_bs & 1) || (y_bs & 1))
+        return VS_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(x) & 3) || (cy > 0 && (reinterpret_cast<uintptr_t>(y) & 3)) || !al16(tokens))
+        return VS_E_INVALID;
+    const long long total = (long long)batch * frames * (height / 2) * (width / 2) * (ld / 8);
+    if (nblk(total, 256) == 0 || (total + 255) / 256 > 0x7fffffffLL) return VS_E_INVALID;
+    hipLaunchKernelGGL(patchify2_kernel, dim3(nblk(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)x, x_bs, cx, (const bf16_t*)y, y_bs, cy, (bf16_t*)tokens, ld, frames, height,
+                       width, total);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+
+extern "C" int vs_gelu_erf(const void* x, void* out, long long n, void* stream) {
+    if (!x || !out || n <= 0 || (reinterpret_cast<uintptr_t>(x) & 1) || (reinterpret_cast<uintptr_t>(out) & 1))
+        return VS_E_INVALID;
+    if ((n + 255) / 256 > 0x7fffffffLL) return VS_E_INVALID;
+    hipLaunchKernelGGL(gelu_erf_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                       (bf16_t*)out, n);
     VS_CHECK_LAUNCH();
     return VS_OK;
 }

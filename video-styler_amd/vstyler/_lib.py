@@ -1,4 +1,4 @@
-"""ctypes binding of libvstyler.so (the C ABI declared in include/vstyler.h).
+"""ctypes binding of libvstyler.so (the C ABI declared in include/vstyler.h and vstyler_image.h).
 
 The product path has no CPU fallback: if the library is missing every op raises.
 """
@@ -117,6 +117,13 @@ SIGNATURES = {
     "vs_sp_comm_destroy": [_P],
     "vs_sp_last_error": [],
 }
+# the image-conditioning entries (include/vstyler_image.h): a second table with the same conventions
+SIGNATURES_IMAGE = {
+    "vs_patchify2": [_P, _LL, _I, _P, _LL, _I, _P, _LL, _I, _I, _I, _I, _P],
+    "vs_gelu_erf": [_P, _P, _LL, _P],
+    "vs_attn_fwd_add": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _LL, _LL, _LL, _LL, _LL, _LL, _LL,
+                        _F, _P],
+}
 _RESTYPES = {"vs_strerror": ctypes.c_char_p, "vs_split_workspace_bytes": ctypes.c_longlong,
              "vs_sp_last_error": ctypes.c_char_p}
 
@@ -132,7 +139,7 @@ def load():
                 f"libvstyler.so not found at {LIB_PATH}: build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or make -C video-styler_amd/csrc)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_IMAGE.items()):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, ctypes.c_int)

@@ -236,15 +236,25 @@ def gemm_fp8(a8, scale_a, w8, out, epilogue=VS_EPI_BIAS, bias=None, residual=Non
     return out
 
 
-def attention(q, k, v, out, num_heads, batch, scale=None):
-    """q/out: [batch*Sq, >=H*128] rows, k/v: [batch*Skv, ...] (views with row strides allowed)."""
+def _attn_geometry(q, k, v, out, batch, shared_kv, name):
+    """Row strides, per-sample row counts and batch strides of an attention call.  shared_kv: k / v hold
+    ONE key set ([Skv, ...] rows) that every batch sample attends to (batch strides 0)."""
     Mq, _, ldq = _rows(q, "q")
     Mk, _, ldk = _rows(k, "k")
     Mv, _, ldv = _rows(v, "v")
     Mo, _, ldo = _rows(out, "out")
-    if Mq % batch or Mk % batch or Mk != Mv or Mo != Mq:
-        raise ValueError("attention: row counts do not match batch")
-    sq, skv = Mq // batch, Mk // batch
+    kb = 1 if shared_kv else batch
+    if Mq % batch or Mk % kb or Mk != Mv or Mo != Mq:
+        raise ValueError(f"{name}: row counts do not match batch")
+    sq, skv = Mq // batch, Mk // kb
+    bsk, bsv = (0, 0) if shared_kv else (skv * ldk, skv * ldv)
+    return sq, skv, (ldq, ldk, ldv, ldo, sq * ldq, bsk, bsv, sq * ldo)
+
+
+def attention(q, k, v, out, num_heads, batch, scale=None, shared_kv=False):
+    """q/out: [batch*Sq, >=H*128] rows, k/v: [batch*Skv, ...] (views with row strides allowed);
+    shared_kv: k/v are [Skv, ...], one key set for every sample."""
+    sq, skv, strides = _attn_geometry(q, k, v, out, batch, shared_kv, "attention")
     hd = 128
     if scale is None:
         scale = hd ** -0.5
@@ -252,8 +262,19 @@ def attention(q, k, v, out, num_heads, batch, scale=None):
     _split_ws(4, q)
     _split_ws(5, q)             # the persistent grid's XCD item queues (zero-filled words)
     _lib.check(_lib.load().vs_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), batch, sq,
-                                       skv, num_heads, hd, ldq, ldk, ldv, ldo, sq * ldq, skv * ldk,
-                                       skv * ldv, sq * ldo, float(scale), _stream(q)))
+                                       skv, num_heads, hd, *strides, float(scale), _stream(q)))
+    return out
+
+
+def attention_add(q, k, v, out, num_heads, batch, scale=None, shared_kv=False):
+    """out = bf16(out + bf16(attention(q, k, v))) in one launch (vs_attn_fwd_add: the checked kernel, at
+    most 1984 keys); arguments as attention()."""
+    sq, skv, strides = _attn_geometry(q, k, v, out, batch, shared_kv, "attention_add")
+    hd = 128
+    if scale is None:
+        scale = hd ** -0.5
+    _lib.check(_lib.load().vs_attn_fwd_add(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), batch, sq,
+                                           skv, num_heads, hd, *strides, float(scale), _stream(q)))
     return out
 
 
@@ -335,6 +356,43 @@ def patchify(lat, out):
     if not lat.is_contiguous() or not out.is_contiguous() or out.numel() != lat.numel():
         raise ValueError("patchify: contiguous tensors of equal numel required")
     _lib.check(_lib.load().vs_patchify(lat.data_ptr(), out.data_ptr(), B, C, T, H, W, _stream(lat)))
+    return out
+
+
+def patchify2(x, y, out):
+    """out [B*S, ld] = im2col of cat([x, y], dim=1) for Conv3d k=s=(1,2,2), columns past 4(cx+cy) zero
+    (vs_patchify2).  x [B or 1, cx, T, H, W], y [B or 1, cy, T, H, W] or None; a batch-1 operand is
+    broadcast over out's B = rows / S."""
+    _req(x, "x")
+    if x.dim() != 5 or not x.is_contiguous():
+        raise ValueError(f"x: expected a contiguous [B, C, T, H, W] tensor, got {tuple(x.shape)}")
+    Bx, cx, T, H, W = x.shape
+    By, cy = 1, 0
+    if y is not None:
+        _req(y, "y")
+        if y.dim() != 5 or not y.is_contiguous() or tuple(y.shape[2:]) != (T, H, W) or y.device != x.device:
+            raise ValueError(f"y: expected a contiguous [B, C, {T}, {H}, {W}] tensor on {x.device}, got {tuple(y.shape)}")
+        By, cy = y.shape[0], y.shape[1]
+    rows, cols, ld = _rows(out, "out")
+    S = T * (H // 2) * (W // 2)
+    if H % 2 or W % 2 or rows % S or cols != ld or cols < 4 * (cx + cy):
+        raise ValueError(f"patchify2: out {tuple(out.shape)} does not hold {S}-token samples of {4 * (cx + cy)} columns")
+    B = rows // S
+    if Bx not in (1, B) or By not in (1, B):
+        raise ValueError(f"patchify2: batch {Bx} / {By} against {B} output samples")
+    _lib.check(_lib.load().vs_patchify2(x.data_ptr(), 0 if Bx == 1 and B > 1 else cx * T * H * W, cx, _ptr(y),
+                                        0 if By == 1 and B > 1 else cy * T * H * W, cy, out.data_ptr(), ld, B, T, H, W,
+                                        _stream(x)))
+    return out
+
+
+def gelu_erf(x, out=None):
+    """out = bf16(gelu(x)) with the erf form of nn.GELU() (vs_gelu_erf); in place by default."""
+    _req(x, "x")
+    out = x if out is None else _req(out, "out")
+    if not x.is_contiguous() or not out.is_contiguous() or out.numel() != x.numel():
+        raise ValueError("gelu_erf: contiguous tensors of equal numel required")
+    _lib.check(_lib.load().vs_gelu_erf(x.data_ptr(), out.data_ptr(), x.numel(), _stream(x)))
     return out
 
 
@@ -492,7 +550,7 @@ def ulysses_permute(src, dst, batch, s_local, world, cols_per_rank, ld_local, js
     return dst
 
 
-__all__ = ["set_option", "get_option", "options", "ulysses_permute", "gemm", "attention", "layernorm_modulate", "rmsnorm_rope", "patchify", "unpatchify", "cfg_euler", "flow_add_noise",
+__all__ = ["set_option", "get_option", "options", "ulysses_permute", "gemm", "attention", "attention_add", "patchify2", "gelu_erf", "layernorm_modulate", "rmsnorm_rope", "patchify", "unpatchify", "cfg_euler", "flow_add_noise",
            "window_gather", "window_blend", "window_finish",
            "time_sinusoid", "mod_add", "axpy", "VS_EPI_BIAS", "VS_EPI_GELU", "VS_EPI_SILU", "VS_EPI_GATE_RES",
            "VS_EPI_RES"]

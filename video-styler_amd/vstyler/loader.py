@@ -16,6 +16,20 @@ WAN_DIT_CONFIGS = {
     "9269f8db9040a9d860eaca435be61814": dict(dim=1536, ffn_dim=8960, num_heads=12, num_layers=30),   # 1.3B
     "aafcfd9672c3a2456dc46e1cb6e52c70": dict(dim=5120, ffn_dim=13824, num_heads=40, num_layers=40),  # 14B
 }
+# The image-conditioned layouts (wan_video_dit.py:537-712): in_dim = 16 + the y channels.  A table of its
+# own, looked up after the one above (whose size tests/test_oracle_kat.py pins).
+WAN_I2V_DIT_CONFIGS = {
+    "6bfcfb3b342cb286ce886889d519a77e": dict(dim=5120, ffn_dim=13824, num_heads=40, num_layers=40, in_dim=36,
+                                             has_image_input=True),                          # I2V-14B
+    "6d6ccde6845b95ad9114ab993d917893": dict(dim=1536, ffn_dim=8960, num_heads=12, num_layers=30, in_dim=36,
+                                             has_image_input=True),                          # Fun-1.3B-InP
+    "3ef3b1f8e1dab83d5b71fd7b617f859f": dict(dim=5120, ffn_dim=13824, num_heads=40, num_layers=40, in_dim=36,
+                                             has_image_input=True, has_image_pos_emb=True),  # FLF2V-14B
+    "5b013604280dd715f8457c6ed6d6a626": dict(dim=5120, ffn_dim=13824, num_heads=40, num_layers=40, in_dim=36,
+                                             has_image_input=False, require_clip_embedding=False),  # Wan2.2-I2V-A14B
+    "349723183fc063b2bfc10bb2835cf677": dict(dim=1536, ffn_dim=8960, num_heads=12, num_layers=30, in_dim=48,
+                                             has_image_input=True),                          # Fun-1.3B-Control
+}
 WAN_COMMON = dict(in_dim=16, out_dim=16, text_dim=4096, freq_dim=256, eps=1e-6, patch_size=(1, 2, 2))
 VACE_14B_HASH = "3b2726384e4f64837bdf216eea3f310d"
 VACE_14B = dict(vace_layers=(0, 5, 10, 15, 20, 25, 30, 35), vace_in_dim=96, patch_size=(1, 2, 2),
@@ -168,7 +182,9 @@ def dit_config_from_shapes(sd):
     if tuple(pe.shape[2:]) != (1, 2, 2):
         return None
     dim = pe.shape[0]
-    return dict(WAN_COMMON, dim=dim, in_dim=pe.shape[1], ffn_dim=sd["blocks.0.ffn.0.weight"].shape[0],
+    image = "blocks.0.cross_attn.k_img.weight" in sd
+    return dict(WAN_COMMON, has_image_input=image, has_image_pos_emb="img_emb.emb_pos" in sd,
+                require_clip_embedding=image, dim=dim, in_dim=pe.shape[1], ffn_dim=sd["blocks.0.ffn.0.weight"].shape[0],
                 num_heads=dim // 128, num_layers=_n_blocks(sd, "blocks"),
                 text_dim=sd["text_embedding.0.weight"].shape[1], freq_dim=sd["time_embedding.0.weight"].shape[1],
                 out_dim=sd["head.head.weight"].shape[0] // 4)
@@ -188,8 +204,8 @@ def vace_config_from_shapes(sd, num_layers):
 def build_dit(state_dict, device):
     sd = {k: v for k, v in state_dict.items() if not k.startswith("vace")}
     h = hash_state_dict_keys(sd)
-    if h in WAN_DIT_CONFIGS:
-        cfg = dict(WAN_COMMON, **WAN_DIT_CONFIGS[h])
+    if h in WAN_DIT_CONFIGS or h in WAN_I2V_DIT_CONFIGS:
+        cfg = dict(WAN_COMMON, **(WAN_DIT_CONFIGS.get(h) or WAN_I2V_DIT_CONFIGS[h]))
     else:
         cfg = dit_config_from_shapes(sd)
         if cfg is None:

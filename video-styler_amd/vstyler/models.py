@@ -183,14 +183,39 @@ class PatchEmbed(nn.Module):
         self.in_dim, self.dim = in_dim, dim
         self.weight = _param(dim, in_dim, 1, 2, 2, device=device)
         self.bias = _param(dim, device=device)
+        self._wpad = self._wpad_of = None
 
-    def forward(self, lat, ws, tag):
+    def padded_weight(self):
+        """The weight as [dim, Kp], Kp = 4 in_dim rounded up to the GEMM's K step of 64, the columns past
+        4 in_dim zero (vs_patchify2 zero-fills the same columns of the token rows: 36 channels give
+        K = 144 in 192).  Built once per loaded weight (rebuilt when the parameter is written again)."""
+        key = (self.weight.data_ptr(), self.weight._version)
+        if self._wpad is None or self._wpad_of != key:
+            k = 4 * self.in_dim
+            wp = torch.zeros((self.dim, (k + 63) // 64 * 64), device=self.weight.device, dtype=BF16)
+            wp[:, :k].copy_(self.weight.detach().reshape(self.dim, k))
+            self._wpad, self._wpad_of = wp, key
+        return self._wpad
+
+    def forward(self, lat, ws, tag, y=None, batch=None):
+        """lat [B, C, T, H, W] -> tokens [B*S, dim].  y [B or 1, in_dim - C, T, H, W]: the channels
+        concatenated behind lat's (wan_video_new.py:1367-1368), read in place by vs_patchify2; with y
+        (or with 4 in_dim no multiple of 64) the token rows and the weight are K-padded.  batch: the
+        output samples when lat and y are batch-1 operands broadcast over the CFG batch."""
         B, C, T, H, W = lat.shape
         S = T * (H // 2) * (W // 2)
-        cols = ws.get(tag + ".cols", (B * S, C * 4))
-        K.patchify(lat.contiguous(), cols)
+        if y is None and batch is None and (C * 4) % 64 == 0:
+            cols = ws.get(tag + ".cols", (B * S, C * 4))
+            K.patchify(lat.contiguous(), cols)
+            out = ws.get(tag + ".out", (B * S, self.dim))
+            K.gemm(cols, self.weight.view(self.dim, C * 4), out, bias=self.bias)
+            return out, (T, H // 2, W // 2)
+        B = B if batch is None else batch
+        wp = self.padded_weight()
+        cols = ws.get(tag + ".cols", (B * S, wp.shape[1]))
+        K.patchify2(lat.contiguous(), None if y is None else y.contiguous(), cols)
         out = ws.get(tag + ".out", (B * S, self.dim))
-        K.gemm(cols, self.weight.view(self.dim, C * 4), out, bias=self.bias)
+        K.gemm(cols, wp, out, bias=self.bias)
         return out, (T, H // 2, W // 2)
 
 
@@ -213,7 +238,7 @@ class AttentionParams(nn.Module):
     row slices of one [n*dim, dim] / [n*dim] buffer, so their projections run as ONE GEMM
     (fused_linear); state-dict loading, LoRA merging and init all write through the slices."""
 
-    def __init__(self, dim, num_heads, device=None, fused=()):
+    def __init__(self, dim, num_heads, device=None, fused=(), image=False):
         super().__init__()
         self.dim, self.num_heads = dim, num_heads
         self.q = Linear(dim, dim, device=device)
@@ -232,6 +257,17 @@ class AttentionParams(nn.Module):
                 lin = getattr(self, name)
                 lin.weight = nn.Parameter(self._fw[i * dim:(i + 1) * dim], requires_grad=False)
                 lin.bias = nn.Parameter(self._fb[i * dim:(i + 1) * dim], requires_grad=False)
+        # the image branch of CrossAttention (wan_video_dit.py:164-167): k_img | v_img fused like k | v
+        self.has_image_input = bool(image)
+        if image:
+            self.k_img = Linear(dim, dim, device=device)
+            self.v_img = Linear(dim, dim, device=device)
+            self.norm_k_img = RMSNormW(dim, device=device)
+            self._fw_img = torch.empty(2 * dim, dim, device=device, dtype=BF16)
+            self._fb_img = torch.empty(2 * dim, device=device, dtype=BF16)
+            for i, lin in enumerate((self.k_img, self.v_img)):
+                lin.weight = nn.Parameter(self._fw_img[i * dim:(i + 1) * dim], requires_grad=False)
+                lin.bias = nn.Parameter(self._fb_img[i * dim:(i + 1) * dim], requires_grad=False)
 
 
 def _fused_views(mod):
@@ -290,6 +326,20 @@ def fused_linear(mod, x, ws, tag):
         K.quant_fp8_rows(x, x8, sc)
         return K.gemm_fp8(x8, sc, W8, out, bias=b, **sw)
     return K.gemm(x, W, out, bias=b)
+
+
+def fused_img_linear(mod, x, ws, tag):
+    """k_img | v_img of the image rows x as one bf16 GEMM into [M, 2 dim], or None when the two no
+    longer alias the fused buffer or carry a hot-loaded LoRA (the caller runs them one by one).  The
+    image projections stay bf16: quantize_fp8_ does not convert them."""
+    d = mod.dim
+    for i, lin in enumerate((mod.k_img, mod.v_img)):
+        if getattr(lin, "lora_A", None) is not None or getattr(lin, "weight_fp8", None) is not None:
+            return None
+        if lin.weight.data_ptr() != mod._fw_img[i * d].data_ptr() or lin.bias is None or \
+                lin.bias.data_ptr() != mod._fb_img[i * d:].data_ptr():
+            return None
+    return K.gemm(x, mod._fw_img, ws.get("fused" + tag, (x.shape[0], 2 * d)), bias=mod._fb_img)
 
 
 class Sequential3(nn.Module):
@@ -375,6 +425,9 @@ def attn_flops(q, k, batch):
     return 4.0 * (q.shape[0] // batch) * (k.shape[0] // batch) * q.shape[1] * batch
 
 
+IMG_TOKENS = 257      # CLIP ViT-H/14 tokens of one image: the rows CrossAttention splits off (:172-174)
+
+
 class RunCtx:
     """Per-forward constants shared by all blocks: batch/token geometry, RoPE table, SP info."""
 
@@ -383,16 +436,19 @@ class RunCtx:
         self.ctx, self.ctx_len, self.ws = ctx, ctx_len, ws
         self.sp = sp                    # vstyler.usp.UlyssesGroup or None
         self.token_offset = token_offset
+        # image conditioning: the embedded CLIP rows every block's image cross-attention reads,
+        # [img_batch * IMG_TOKENS, D] (img_batch 1: one key set shared by every CFG sample), or None
+        self.img, self.img_batch = None, 0
 
 
 class DiTBlock(nn.Module):
     """wan_video_dit.py:196-230 parameters; forward = fused kernel sequence on [B*S, D] rows."""
 
-    def __init__(self, dim, num_heads, ffn_dim, eps=1e-6, device=None):
+    def __init__(self, dim, num_heads, ffn_dim, eps=1e-6, device=None, has_image_input=False):
         super().__init__()
         self.dim, self.num_heads, self.ffn_dim, self.eps = dim, num_heads, ffn_dim, eps
         self.self_attn = AttentionParams(dim, num_heads, device, fused=("q", "k", "v"))
-        self.cross_attn = AttentionParams(dim, num_heads, device, fused=("k", "v"))
+        self.cross_attn = AttentionParams(dim, num_heads, device, fused=("k", "v"), image=has_image_input)
         self.norm3 = LayerNormAffine(dim, device)
         self.ffn = Sequential3(Linear(dim, ffn_dim, device=device), Linear(ffn_dim, dim, device=device))
         self.modulation = _param(1, 6, dim, device=device)
@@ -458,6 +514,8 @@ class DiTBlock(nn.Module):
         r0, M = b0 * S, nb * S
         p = dict(nb=nb, M=M, x=x[r0:r0 + M], mod=mod[b0:b0 + nb], ctx=rc.ctx[b0 * L:(b0 + nb) * L],
                  hint=None if hint is None else hint[r0:r0 + M], tag=tag)
+        if rc.img is not None:          # this part's image rows: the shared set, or its samples' own
+            p["img"] = rc.img if rc.img_batch == 1 else rc.img[b0 * IMG_TOKENS:(b0 + nb) * IMG_TOKENS]
         for n in ("h", "q", "k", "v", "o"):     # row slices of the all-samples buffers
             p[n] = ws.get(n, (rc.batch * S, D))[r0:r0 + M]
         return p
@@ -525,6 +583,8 @@ class DiTBlock(nn.Module):
             linear(ca.v, p["ctx"], vc, ws)
         K.rmsnorm_rope(kc, ca.norm_k.weight, eps)
         K.attention(q, kc, vc, o, self.num_heads, nb)
+        if ca.has_image_input:
+            self._image_attn(p, rc, q, o)
         linear(ca.o, o, x, ws, epilogue=K.VS_EPI_RES, residual=x)
         # --- FFN (wan_video_dit.py:228-229) + VACE hint (wan_video_new.py:1450)
         h = ln_into(x, h, ws, self.ffn[0], eps, shift=mod[:, 3], scale=mod[:, 4], mod_bstride=6 * D,
@@ -533,6 +593,33 @@ class DiTBlock(nn.Module):
         linear(self.ffn[0], h, f, ws, epilogue=K.VS_EPI_GELU)
         linear(self.ffn[2], f, x, ws, epilogue=K.VS_EPI_GATE_RES, residual=x,
                gate=mod[:, 5], gate_bstride=6 * D, rows_per_batch=S, hint=p["hint"], hint_scale=hint_scale)
+
+
+    def _image_attn(self, p, rc, q, o):
+        """o += attention(q, k_img, v_img) over the 257 embedded image tokens (wan_video_dit.py:181-185),
+        after the text attention has written o.  k_img | v_img come from one GEMM over the image rows
+        -- once for all CFG samples when they share the image (key batch stride 0).  Host option
+        img_attn_fused 1: vs_attn_fwd_add adds in its O store; 0: attention into a scratch buffer and
+        an axpy pass (kernels that predate the fused one; bit-identical with attn_nc=0, attn_impl=8)."""
+        ws, D, eps, nb, ca = rc.ws, self.dim, self.eps, p["nb"], self.cross_attn
+        img = p.get("img")
+        if img is None:
+            raise ValueError("a DiT with has_image_input needs clip_feature (the embedded image tokens)")
+        shared = rc.img_batch == 1
+        kv = fused_img_linear(ca, img, ws, "kvi" + p["tag"])
+        if kv is not None:
+            ki, vi = kv[:, :D], kv[:, D:]
+        else:
+            ki, vi = ws.get("ki" + p["tag"], (img.shape[0], D)), ws.get("vi" + p["tag"], (img.shape[0], D))
+            linear(ca.k_img, img, ki, ws)
+            linear(ca.v_img, img, vi, ws)
+        K.rmsnorm_rope(ki, ca.norm_k_img.weight, eps)
+        if host_option("img_attn_fused"):
+            K.attention_add(q, ki, vi, o, self.num_heads, nb, shared_kv=shared)
+        else:
+            oi = ws.get("o_img", (rc.batch * rc.seq, D))[:p["M"]]
+            K.attention(q, ki, vi, oi, self.num_heads, nb, shared_kv=shared)
+            K.axpy(o, oi, 1.0)
 
 
 class Head(nn.Module):
@@ -566,32 +653,105 @@ def rope_table(head_dim=128, end=1024, theta=10000.0, device=None):
     return tab.to(device)
 
 
+class ImgEmbProj(nn.Module):
+    """MLP.proj (wan_video_dit.py:235-241): LayerNorm, Linear, GELU, Linear, LayerNorm at indices 0, 1, 3, 4."""
+
+    def __init__(self, in_dim, out_dim, device=None):
+        super().__init__()
+        self.add_module("0", LayerNormAffine(in_dim, device))
+        self.add_module("1", Linear(in_dim, in_dim, device=device))
+        self.add_module("3", Linear(in_dim, out_dim, device=device))
+        self.add_module("4", LayerNormAffine(out_dim, device))
+
+    def __getitem__(self, i):
+        return getattr(self, str(i))
+
+
+class ImgEmb(nn.Module):
+    """MLP(1280, dim, has_pos_emb) parameters (wan_video_dit.py:232-249): the CLIP-feature embedding."""
+
+    def __init__(self, in_dim, out_dim, has_pos_emb=False, device=None):
+        super().__init__()
+        self.in_dim, self.out_dim = in_dim, out_dim
+        self.proj = ImgEmbProj(in_dim, out_dim, device)
+        self.has_pos_emb = has_pos_emb
+        if has_pos_emb:
+            self.emb_pos = _param(1, 2 * IMG_TOKENS, in_dim, device=device)
+
+
+CLIP_DIM = 1280       # clip_feature_dim (wan_video_dit.py:322)
+IMG_EMB_EPS = 1e-5    # nn.LayerNorm's default eps, which MLP.proj's two LayerNorms keep
+
+
 class WanModel(nn.Module):
-    """wan_video_dit.py:272-337 (has_image_input=False path used by Wan2.1-VACE / T2V)."""
+    """wan_video_dit.py:272-337: the T2V / VACE layout (in_dim 16) and the image-conditioned ones --
+    in_dim > 16 (the VAE-embedded image `y` concatenated behind the latents: I2V, FLF2V, Fun-InP,
+    Wan2.2-I2V-A14B) with or without the CLIP image branch (has_image_input: img_emb + the blocks'
+    k_img / v_img / norm_k_img; has_image_pos_emb: img_emb.emb_pos over 514 tokens)."""
 
     def __init__(self, dim, in_dim, ffn_dim, out_dim, text_dim, freq_dim, eps, patch_size, num_heads,
-                 num_layers, has_image_input=False, device=None, **kwargs):
+                 num_layers, has_image_input=False, has_image_pos_emb=False, has_ref_conv=False,
+                 add_control_adapter=False, seperated_timestep=False, require_vae_embedding=True,
+                 require_clip_embedding=True, fuse_vae_embedding_in_latents=False, device=None, **kwargs):
         super().__init__()
-        if has_image_input:
-            raise NotImplementedError("image-conditioned Wan (I2V/FLF2V) is outside the Ditto hot path")
+        for name, on in (("has_ref_conv", has_ref_conv), ("add_control_adapter", add_control_adapter),
+                         ("seperated_timestep", seperated_timestep),
+                         ("fuse_vae_embedding_in_latents", fuse_vae_embedding_in_latents)):
+            if on:
+                raise NotImplementedError(f"WanModel({name}=True) (Fun-Control reference conv, camera control, "
+                                          f"TI2V-5B) is not in this build")
         if dim // num_heads != 128:
             raise NotImplementedError("head_dim must be 128 (all Wan2.1 models)")
+        if in_dim < 16:
+            raise ValueError(f"in_dim {in_dim}: the 16 latent channels come first")
+        if has_image_pos_emb and not has_image_input:
+            raise ValueError("has_image_pos_emb needs has_image_input")
         self.dim, self.in_dim, self.ffn_dim, self.out_dim = dim, in_dim, ffn_dim, out_dim
         self.text_dim, self.freq_dim, self.eps, self.num_heads = text_dim, freq_dim, eps, num_heads
         self.patch_size = tuple(patch_size)
-        self.has_image_input = False
+        self.has_image_input = bool(has_image_input)
+        self.has_image_pos_emb = bool(has_image_pos_emb)
         self.seperated_timestep = False
-        self.require_vae_embedding = True
-        self.require_clip_embedding = True
+        self.require_vae_embedding = bool(require_vae_embedding)
+        self.require_clip_embedding = bool(require_clip_embedding)
         self.fuse_vae_embedding_in_latents = False
         self.patch_embedding = PatchEmbed(in_dim, dim, device)
         self.text_embedding = Sequential3(Linear(text_dim, dim, device=device), Linear(dim, dim, device=device))
         self.time_embedding = Sequential3(Linear(freq_dim, dim, device=device), Linear(dim, dim, device=device))
         self.time_projection = nn.Module()
         self.time_projection.add_module("1", Linear(dim, 6 * dim, device=device))
-        self.blocks = nn.ModuleList([DiTBlock(dim, num_heads, ffn_dim, eps, device) for _ in range(num_layers)])
+        self.blocks = nn.ModuleList([DiTBlock(dim, num_heads, ffn_dim, eps, device, has_image_input=has_image_input)
+                                     for _ in range(num_layers)])
         self.head = Head(dim, out_dim, patch_size, eps, device)
+        if has_image_input:
+            self.img_emb = ImgEmb(CLIP_DIM, dim, has_pos_emb=has_image_pos_emb, device=device)
         self._rope = None
+
+    def img_embed(self, clip_feature, ws):
+        """clip_feature [Bc, N, 1280] -> [Bc*N, D]: MLP.forward (wan_video_dit.py:246-249) as
+        [+ emb_pos], LayerNorm-affine over 1280, Linear, erf-GELU, Linear, LayerNorm-affine over D; every
+        step rounds to bf16 as the reference's bf16 modules do."""
+        e = self.img_emb
+        Bc, N, C = clip_feature.shape
+        if C != CLIP_DIM or N not in (IMG_TOKENS, 2 * IMG_TOKENS):
+            raise ValueError(f"clip_feature: expected [B, {IMG_TOKENS} or {2 * IMG_TOKENS}, {CLIP_DIM}], got "
+                             f"{tuple(clip_feature.shape)}")
+        x = clip_feature.to(BF16).contiguous()
+        if e.has_pos_emb:
+            if N != 2 * IMG_TOKENS:     # x + emb_pos (1, 514, 1280) broadcasts over the batch only (:247-248)
+                raise ValueError(f"img_emb.emb_pos covers {2 * IMG_TOKENS} tokens, clip_feature has {N}")
+            x = K.mod_add(e.emb_pos.view(N, C), x, ws.get("img_x", (Bc, N, C)), N * C, C)
+        M = Bc * N
+        h = ws.get("img_h", (M, C))
+        K.layernorm_modulate(x.view(M, C), h, IMG_EMB_EPS, weight=e.proj[0].weight, bias=e.proj[0].bias)
+        u = ws.get("img_u", (M, C))
+        K.gemm(h, e.proj[1].weight, u, bias=e.proj[1].bias)
+        K.gelu_erf(u)
+        v = ws.get("img_v", (M, self.dim))
+        K.gemm(u, e.proj[3].weight, v, bias=e.proj[3].bias)
+        out = ws.get("img_emb", (M, self.dim))
+        K.layernorm_modulate(v, out, IMG_EMB_EPS, weight=e.proj[4].weight, bias=e.proj[4].bias)
+        return out
 
     def rope(self, device):
         if self._rope is None or self._rope.device != torch.device(device):

@@ -20,10 +20,14 @@ option), read once when the package is imported.
   cfg_prefix      1      the first DiT block's and the first VACE block's phases 1-3 (LN1, q|k|v,
                          self-attention, o-proj, LN3) run once for both CFG samples when their rows are
                          equal (shared latents / timestep / VACE context): bit-identical (DiTBlock)
+  img_attn_fused  1      image cross-attention of an I2V DiT: 1 adds into o inside the attention kernel
+                         (vs_attn_fwd_add), 0 attention into a scratch buffer + an axpy pass (the kernels
+                         that predate it); bit-identical results (DiTBlock._image_attn)
 """
 HOST_DEFAULTS = {
     "sp_overlap": 1, "sp_comm": "torch", "sp_comm_stream": "side", "sp_graph": 0, "sp_rows": 1,
     "sp_merge_ffn": 1, "cfg_parallel": "0", "ws_poison": 0, "graph": 1, "cfg_prefix": 1,
+    "img_attn_fused": 1,
 }
 _CHOICES = {"sp_comm": ("torch", "native"), "sp_comm_stream": ("side", "caller"),
             "cfg_parallel": ("0", "1", "auto")}

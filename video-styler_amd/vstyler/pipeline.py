@@ -15,7 +15,7 @@ import torch
 
 from . import kernels as K
 from .flow_match import FlowMatchScheduler
-from .models import RunCtx, Workspace, WanModel, VaceWanModel
+from .models import IMG_TOKENS, RunCtx, Workspace, WanModel, VaceWanModel
 from .options import host_option
 from .window import check_window_args, plan_windows
 
@@ -31,7 +31,7 @@ def _workspace(device):
     return _WS[key]
 
 
-_UNSUPPORTED = ("clip_feature", "y", "reference_latents", "audio_embeds", "motion_latents", "s2v_pose_latents",
+_UNSUPPORTED = ("reference_latents", "audio_embeds", "motion_latents", "s2v_pose_latents",
                 "motion_bucket_id", "pose_latents", "face_pixel_values", "control_camera_latents_input")
 
 _WINDOW_PLANS = {}
@@ -56,13 +56,15 @@ def slice_windows(x, plan):
 
 
 def _windowed_forward(size, stride, dit, motion_controller, vace, animate_adapter, latents, vace_context,
-                      vace_context_windows, **fwd):
+                      vace_context_windows, y=None, y_windows=None, **fwd):
     """TemporalTiler_BCTHW.run (wan_video_new.py:1229-1256) around the plain forward: every window
     [t, t_) of the latent time axis is an ordinary forward of latents[:, :, t:t_] (RoPE positions
     0..t_-t-1, same timestep and context), blended into `value` with the window's mask and divided by
     the accumulated weight at the end, in the reference's bf16 arithmetic (vs_window_blend /
     vs_window_finish).  Unlike the reference, whose tiler slices only latents and y, vace_context is
-    cut with the same [t, t_): a full-length context does not match the window's tokens."""
+    cut with the same [t, t_): a full-length context does not match the window's tokens.  y (the image
+    conditioning channels) is cut per window as the reference's tiler does (its tensor_names list y),
+    or comes pre-cut as y_windows."""
     device = latents.device
     ws = _workspace(device)
     lat = latents.to(BF16).contiguous()
@@ -71,15 +73,23 @@ def _windowed_forward(size, stride, dit, motion_controller, vace, animate_adapte
     use_vace = vace_context is not None and vace is not None
     if use_vace and vace_context_windows is None:
         vc = vace_context.to(BF16).contiguous()
+    if y is not None and y_windows is None:
+        yc = y.to(BF16).contiguous()
     value = None
     for i, (t, t_) in enumerate(plan.windows):
         lw = K.window_gather(lat, t, ws.get("win_lat", (Bl, C, t_ - t, H, W)))
+        yw = None
+        if y_windows is not None:
+            yw = y_windows[i]
+        elif y is not None:
+            yw = K.window_gather(yc, t, ws.get("win_y", (yc.shape[0], yc.shape[1], t_ - t, H, W)))
         vw = None
         if use_vace and vace_context_windows is not None:
             vw = vace_context_windows[i]
         elif use_vace:
             vw = K.window_gather(vc, t, ws.get("win_vace", (vc.shape[0], vc.shape[1], t_ - t, H, W)))
-        out = model_fn_wan_video(dit, motion_controller, vace, animate_adapter, latents=lw, vace_context=vw, **fwd)
+        out = model_fn_wan_video(dit, motion_controller, vace, animate_adapter, latents=lw, vace_context=vw, y=yw,
+                                 **fwd)
         if value is None:
             value = torch.zeros((out.shape[0], out.shape[1], T, H, W), device=device, dtype=BF16)
         K.window_blend(out, masks[i], value, t)
@@ -90,7 +100,8 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
                        latents: torch.Tensor = None, timestep: torch.Tensor = None, context: torch.Tensor = None,
                        vace_context=None, vace_scale=1.0, use_unified_sequence_parallel: bool = False,
                        sp_group=None, slg_blocks=(), tea_cache=None, cfg_sample=0, sliding_window_size=None,
-                       sliding_window_stride=None, vace_context_windows=None, **kwargs):
+                       sliding_window_stride=None, vace_context_windows=None, y=None, clip_feature=None,
+                       y_windows=None, **kwargs):
     """One DiT(+VACE) forward (wan_video_new.py:1338-1468) -> [B,16,T,H,W] bf16 velocity.
 
     slg_blocks: skip-layer guidance (config 5, ComfyUI WanVideoSLG): the listed main blocks are
@@ -108,7 +119,16 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     sliding_window_size / sliding_window_stride (latent frames, both ints, 1 <= stride <= size): the
     temporal sliding window of wan_video_new.py:1291-1315 (_windowed_forward).  stride alone is
     ignored, as in the reference.  One window (size >= T) takes the plain path.  vace_context_windows:
-    the vace_context already cut per window (slice_windows), so a denoising loop gathers it once."""
+    the vace_context already cut per window (slice_windows), so a denoising loop gathers it once.
+
+    Image conditioning (wan_video_new.py:1366-1371).  y [1 or B, dit.in_dim - 16, T, H, W]: the mask +
+    VAE-encoded image channels, concatenated behind the latents when dit.require_vae_embedding (read
+    in place by the patch embedding; y_windows: y pre-cut per window).  clip_feature [1 or B, 257 or
+    514, 1280]: CLIP image features, embedded by dit.img_emb when dit.require_clip_embedding and
+    dit.has_image_input; the first 257 embedded rows are the blocks' image keys, any further rows join
+    the text keys (wan_video_dit.py:172-174).  A DiT with in_dim > 16 needs y and one with
+    has_image_input needs clip_feature: ValueError otherwise (the reference would feed the patch
+    embedding too few channels / attend to the first 257 text rows as the image)."""
     for name in _UNSUPPORTED:
         if kwargs.get(name) is not None:
             raise NotImplementedError(f"model_fn_wan_video: '{name}' is outside the Ditto hot path")
@@ -119,9 +139,24 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
             # residuals across different windows
             raise NotImplementedError("model_fn_wan_video: tea_cache with a temporal sliding window")
         return _windowed_forward(win[0], win[1], dit, motion_controller, vace, animate_adapter, latents, vace_context,
-                                 vace_context_windows, timestep=timestep, context=context, vace_scale=vace_scale,
+                                 vace_context_windows, y=y, y_windows=y_windows, clip_feature=clip_feature,
+                                 timestep=timestep, context=context, vace_scale=vace_scale,
                                  use_unified_sequence_parallel=use_unified_sequence_parallel, sp_group=sp_group,
                                  slg_blocks=slg_blocks, cfg_sample=cfg_sample, **kwargs)
+    if y is not None and not dit.require_vae_embedding:
+        y = y_windows = None
+    use_clip = clip_feature is not None and dit.require_clip_embedding and dit.has_image_input
+    if not use_clip:
+        clip_feature = None
+    if dit.has_image_input and clip_feature is None:
+        raise ValueError("model_fn_wan_video: this DiT has the image cross-attention branch (has_image_input): "
+                         "pass clip_feature= (the CLIP image features, [1 or B, 257 or 514, 1280])")
+    if y is not None and 16 + y.shape[1] != dit.in_dim:
+        raise ValueError(f"model_fn_wan_video: y has {y.shape[1]} channels, the DiT's patch embedding takes "
+                         f"16 + {dit.in_dim - 16}")
+    if y is None and dit.in_dim > 16:
+        raise ValueError(f"model_fn_wan_video: the DiT's patch embedding takes {dit.in_dim} channels: pass y= "
+                         f"({dit.in_dim - 16} image-conditioning channels)")
     if use_unified_sequence_parallel:
         from .usp import CfgParallel, get_default_group
         plan = sp_group if sp_group is not None else get_default_group()
@@ -138,7 +173,8 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
                                            timestep=mine(ts), context=context[c:c + 1],
                                            vace_context=mine(vace_context), vace_scale=vace_scale,
                                            use_unified_sequence_parallel=plan.ulysses is not None,
-                                           sp_group=plan.ulysses, slg_blocks=slg_blocks, cfg_sample=c, **kwargs)
+                                           sp_group=plan.ulysses, slg_blocks=slg_blocks, cfg_sample=c, y=mine(y),
+                                           clip_feature=mine(clip_feature), **kwargs)
                 out = torch.empty((2,) + tuple(local.shape[1:]), device=local.device, dtype=local.dtype)
                 plan.gather_cfg(out, local)
                 return out
@@ -148,9 +184,16 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     # every CFG sample starts from the same rows when the latents, the timestep (and the VACE context)
     # are shared (the cfg_merge broadcast below): the first blocks' self-attention halves are then
     # computed once for all samples (DiTBlock shared_prefix)
-    shared = B > 1 and latents.shape[0] == 1 and timestep.numel() == 1
+    shared = B > 1 and latents.shape[0] == 1 and timestep.numel() == 1 and (y is None or y.shape[0] == 1)
     shared_vace = shared and vace_context is not None and vace_context.shape[0] == 1
-    if latents.shape[0] != B:
+    if y is not None:
+        if y.shape[0] not in (1, B) or tuple(y.shape[2:]) != tuple(latents.shape[2:]):
+            raise ValueError(f"model_fn_wan_video: y {tuple(y.shape)} does not match latents {tuple(latents.shape)} "
+                             f"(batch 1 or {B})")
+        y = y.to(device=device, dtype=BF16)
+    if clip_feature is not None and clip_feature.shape[0] not in (1, B):
+        raise ValueError(f"model_fn_wan_video: clip_feature batch {clip_feature.shape[0]} (1 or {B})")
+    if latents.shape[0] != B and y is None:
         latents = latents.expand(B, *latents.shape[1:])
     latents = latents.to(BF16).contiguous()
     timestep = timestep.reshape(-1).to(device=device, dtype=BF16)
@@ -159,8 +202,28 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
 
     t, t_mod = dit.time_embed(timestep, ws)
     ctx = dit.text_embed(context.to(BF16), ws)
-    x, grid = dit.patch_embedding(latents, ws, "x")
+    if y is None:
+        x, grid = dit.patch_embedding(latents, ws, "x")
+    else:       # cat([latents, y], dim=1) read in place; batch-1 operands broadcast over the CFG batch
+        x, grid = dit.patch_embedding(latents, ws, "x", y=y, batch=B)
     S = grid[0] * grid[1] * grid[2]
+    img = None
+    if clip_feature is not None:
+        # context = cat([img_emb(clip_feature), text]) split as CrossAttention.forward does: the first
+        # 257 rows are the image keys, the rest (the second image of a 514-row feature) text keys
+        emb = dit.img_embed(clip_feature.to(device), ws)
+        Bc, N, D = clip_feature.shape[0], clip_feature.shape[1], dit.dim
+        emb = emb.view(Bc, N, D)
+        img = emb[:, :IMG_TOKENS]
+        if N > IMG_TOKENS:
+            extra = N - IMG_TOKENS
+            img = ws.get("img_keys", (Bc, IMG_TOKENS, D))
+            img.copy_(emb[:, :IMG_TOKENS])
+            ctx2 = ws.get("ctx_img", (B, extra + L, D))       # built once per forward
+            ctx2[:, :extra].copy_(emb[:, IMG_TOKENS:].expand(B, extra, D))
+            ctx2[:, extra:].copy_(ctx.view(B, L, D))
+            ctx, L = ctx2.view(B * (extra + L), D), extra + L
+        img = img.reshape(Bc * IMG_TOKENS, D)
 
     sp = None
     if use_unified_sequence_parallel:
@@ -171,6 +234,8 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
         if sp is not None and sp.world_size == 1 and not getattr(sp, "force_collectives", False):
             sp = None
     rc = RunCtx(B, S, grid, dit.rope(device), ctx, L, ws)
+    if img is not None:
+        rc.img, rc.img_batch = img, clip_feature.shape[0]
 
     vace_x = None
     if vace_context is not None and vace is not None:
@@ -208,6 +273,32 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     lat = torch.empty((B, dit.out_dim, T, 2 * H2, 2 * W2), device=device, dtype=BF16)
     K.unpatchify(out, lat)
     return lat
+
+
+def image_mask(num_frames, h, w, has_end=False, device=None, dtype=BF16):
+    """The 4 mask channels of y (wan_video_new.py:709-720) -> (4, T', h, w), T' = (num_frames + 3) / 4:
+    pixel frame f is known (1) when it is the input image (f = 0) or the end image (f = num_frames - 1),
+    the first frame counts four times, and latent frame t's channel c is frame 4t + c of that list."""
+    known = torch.zeros(num_frames + 3, dtype=dtype, device=device)
+    known[:4] = 1
+    if has_end:
+        known[-1] = 1
+    if known.numel() % 4:
+        raise ValueError(f"num_frames must be 4k + 1, got {num_frames}")
+    return known.view(-1, 4).t()[:, :, None, None].expand(4, known.numel() // 4, h, w).contiguous()
+
+
+def image_vae_input(image, end_image, num_frames):
+    """The VAE input of the image embedder (wan_video_new.py:713-717): image (and end_image) are
+    normalised (1, 3, 1, H, W) frames; the frames between / after them are zeros -> (1, 3, num_frames, H, W)."""
+    B, C, _, H, W = image.shape
+    gap = num_frames - (1 if end_image is None else 2)
+    if gap < 0:
+        raise ValueError(f"num_frames {num_frames} cannot hold the input and end images")
+    parts = [image, torch.zeros((B, C, gap, H, W), dtype=image.dtype, device=image.device)]
+    if end_image is not None:
+        parts.append(end_image)
+    return torch.cat(parts, dim=2)
 
 
 @dataclass
@@ -527,8 +618,11 @@ class WanVideoPipeline:
     def denoise(self, latents, context_posi, context_nega, vace_context=None, vace_scale=1.0, cfg_scale=5.0,
                 num_inference_steps=50, sigma_shift=5.0, denoising_strength=1.0, progress_bar_cmd=None,
                 use_graph=None, tea_cache=None, sliding_window_size=None, sliding_window_stride=None,
-                switch_DiT_boundary=0.875):
+                switch_DiT_boundary=0.875, y=None, clip_feature=None):
         """The loop of wan_video_new.py:515-542 (cfg_merge batched), returns the final latents.
+
+        y / clip_feature: the image conditioning of an I2V DiT (model_fn_wan_video), constant over the
+        steps and handed to both experts; y is cut per window once, like the vace_context.
 
         Step 0 runs eagerly (it also sizes the Workspace); the whole step -- model_fn (DiT + VACE,
         CFG as one batch-2 forward) + fused CFG/Euler update -- is then captured once into a hipGraph
@@ -556,7 +650,8 @@ class WanVideoPipeline:
             # the reference hands one TeaCache state to both experts and has no coefficients for them
             raise NotImplementedError("tea_cache_l1_thresh with a second expert (dit2) is not supported")
         window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context,
-                                        tea_cache)
+                                        tea_cache, y=y)
+        image_kw = self._image_kwargs(y, clip_feature)
         self.scheduler.set_timesteps(num_inference_steps, denoising_strength=denoising_strength, shift=sigma_shift)
         n_steps = len(self.scheduler.timesteps)
         segments = plan_experts(self.scheduler.timesteps, switch_DiT_boundary, has2)
@@ -582,7 +677,7 @@ class WanVideoPipeline:
                 v = self.model_fn(dit=dit, vace=vace, latents=latents, timestep=t_buf, context=ctx,
                                   vace_context=vace_context, vace_scale=vace_scale,
                                   use_unified_sequence_parallel=self.use_unified_sequence_parallel,
-                                  sp_group=self.sp_group, tea_cache=tea_cache, **window_kw)
+                                  sp_group=self.sp_group, tea_cache=tea_cache, **window_kw, **image_kw)
                 K.cfg_euler_dev(v[0:1], v[1:2] if use_cfg else None, latents, scale, d_buf)
             return step
 
@@ -609,7 +704,16 @@ class WanVideoPipeline:
         self.last_graph = self.last_graphs[-1]
         return latents
 
-    def _window_kwargs(self, T, size, stride, vace_context, tea_cache=None):
+    def _image_kwargs(self, y, clip_feature):
+        """model_fn's image-conditioning arguments as device bf16 tensors ({} without them)."""
+        kw = {}
+        if y is not None:
+            kw["y"] = y.to(device=self.device, dtype=BF16).contiguous()
+        if clip_feature is not None:
+            kw["clip_feature"] = clip_feature.to(device=self.device, dtype=BF16).contiguous()
+        return kw
+
+    def _window_kwargs(self, T, size, stride, vace_context, tea_cache=None, y=None):
         """model_fn's sliding-window arguments for a loop over T latent frames ({} without windows)."""
         win = check_window_args(size, stride)
         if win is None:
@@ -622,12 +726,15 @@ class WanVideoPipeline:
             if vace_context is not None and (self.vace is not None or
                                              (self.dit2 is not None and self.vace2 is not None)):
                 kw["vace_context_windows"] = slice_windows(vace_context.to(self.device), plan)
+            if y is not None:
+                kw["y_windows"] = slice_windows(y.to(self.device), plan)
         return kw
 
     def denoise_unipc(self, latents, context_posi, context_nega, vace_context=None, vace_scale=1.0,
                       cfg_scale=1.2, num_inference_steps=4, sigma_shift=2.0, slg_blocks=(), slg_range=(0.2, 0.7),
                       progress_bar_cmd=None, input_latents=None, forward_step=None, skip_backward_step=None,
-                      sliding_window_size=None, sliding_window_stride=None, switch_DiT_boundary=0.875):
+                      sliding_window_size=None, sliding_window_stride=None, switch_DiT_boundary=0.875,
+                      y=None, clip_feature=None):
         """Config 5's sampler (ditto_comfyui_workflow.json WanVideoSampler 4 / 1.2 / 2.0 / unipc with
         WanVideoSLG): FlowUniPCMultistepScheduler (vstyler.unipc) on fp32 latents, CFG as one
         batch-2 forward, skip-layer guidance on the uncond sample for step fractions in slg_range.
@@ -649,7 +756,9 @@ class WanVideoPipeline:
         from .experts import expert_cfg_scales, plan_experts
         has2 = self.dit2 is not None
         scales = expert_cfg_scales(cfg_scale, has2)
-        window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context)
+        window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context,
+                                        y=y)
+        window_kw.update(self._image_kwargs(y, clip_feature))       # (y / clip_feature: as in denoise)
         from .unipc import FlowUniPCMultistepScheduler, cast
         sched = FlowUniPCMultistepScheduler(shift=1.0)
         sched.set_timesteps(num_inference_steps, shift=sigma_shift)
@@ -708,16 +817,18 @@ class WanVideoPipeline:
                  tea_cache_model_id="", progress_bar_cmd=None,
                  # extensions of this build (the DiT path without T5/VAE):
                  prompt_emb=None, negative_prompt_emb=None, vace_context=None, output_type="video",
-                 input_latents=None, **kwargs):
-        """wan_video_new.py:416-560 for the Ditto path (T2V/VACE/video-to-video, no image/audio/camera
-        inputs).  With dit2 loaded the steps below switch_DiT_boundary run on dit2 / vace2 and cfg_scale
+                 input_latents=None, clip_feature=None, **kwargs):
+        """wan_video_new.py:416-560 for the Ditto path (T2V/VACE/video-to-video) and image-to-video (no
+        audio/camera inputs).  input_image (and end_image) on a DiT with in_dim > 16 become y
+        (encode_input_image) for both experts; a DiT that also takes CLIP features (has_image_input with
+        require_clip_embedding: the Wan2.1 I2V / FLF2V / Fun-InP checkpoints) needs them precomputed as
+        clip_feature= [1, 257 or 514, 1280] -- this build has no image_encoder.  With dit2 loaded the steps below switch_DiT_boundary run on dit2 / vace2 and cfg_scale
         may be a (low_noise, high_noise) pair (denoise).  input_video (or its precomputed latents input_latents (1, 16, T', h, w)) with
         denoising_strength < 1 starts the loop from the video's latents re-noised to the first sigma
         of the shortened schedule (WanVideoUnit_InputVideoEmbedder, :591-614)."""
-        for name, val in (("input_image", input_image), ("end_image", end_image),
-                          ("motion_bucket_id", motion_bucket_id)):
-            if val is not None:
-                raise NotImplementedError(f"{name} is outside the Ditto hot path of this build")
+        if motion_bucket_id is not None:
+            raise NotImplementedError("motion_bucket_id is outside the Ditto hot path of this build")
+        self._check_image_args(input_image, end_image, clip_feature)
         if input_video is not None and input_latents is not None:
             raise ValueError("pass input_video or its precomputed input_latents, not both")
         check_window_args(sliding_window_size, sliding_window_stride)
@@ -749,6 +860,9 @@ class WanVideoPipeline:
         if vace_context is None and (vace_video is not None or vace_video_mask is not None or nref):
             vace_context = self.encode_vace(vace_video, vace_video_mask, height, width, num_frames, tiled,
                                             tile_size, tile_stride, vace_reference_image)
+        y = None
+        if input_image is not None:
+            y = self.encode_input_image(input_image, end_image, num_frames, height, width, tiled, tile_size, tile_stride)
         tea_cache = None
         if tea_cache_l1_thresh is not None:                # WanVideoUnit_TeaCache (:936-947)
             from .teacache import TeaCache
@@ -758,7 +872,8 @@ class WanVideoPipeline:
                                None if vace_context is None else vace_context.to(self.device), vace_scale,
                                cfg_scale, num_inference_steps, sigma_shift, denoising_strength, progress_bar_cmd,
                                tea_cache=tea_cache, sliding_window_size=sliding_window_size,
-                               sliding_window_stride=sliding_window_stride, switch_DiT_boundary=switch_DiT_boundary)
+                               sliding_window_stride=sliding_window_stride, switch_DiT_boundary=switch_DiT_boundary,
+                               y=y, clip_feature=clip_feature)
         self.last_tea_cache = tea_cache
         if nref:                                            # :545-550
             latents = latents[:, :, nref:].contiguous()
@@ -827,6 +942,53 @@ class WanVideoPipeline:
         if self.text_encoder is None or self.prompter is None:
             raise NotImplementedError("T5 text encoder not loaded: pass prompt_emb=/negative_prompt_emb=")
         return self.prompter.encode_prompt(prompt, device=self.device)
+
+    def _check_image_args(self, input_image, end_image, clip_feature):
+        """The image arguments of __call__ against the loaded DiTs, before anything is encoded."""
+        dits = [d for d in (self.dit, self.dit2) if d is not None]
+        if end_image is not None and input_image is None:
+            raise ValueError("end_image needs input_image")
+        if input_image is not None:
+            for d in dits:
+                if d.in_dim <= 16 or not d.require_vae_embedding:
+                    raise ValueError(f"input_image needs an image-to-video DiT (in_dim > 16); the loaded DiT has "
+                                     f"in_dim {d.in_dim}")
+                if d.in_dim != 36:
+                    raise NotImplementedError(f"input_image gives the 4 + 16 channels of an in_dim 36 DiT; in_dim "
+                                              f"{d.in_dim} (Fun-Control) also needs control latents")
+        for d in dits:
+            if d.has_image_input and d.require_clip_embedding and clip_feature is None and \
+                    (input_image is not None or d.in_dim > 16):
+                raise ValueError("this DiT attends to CLIP image features: pass clip_feature= ([1, 257 or 514, 1280], "
+                                 "the CLIP ViT-H features of the input image); this build has no image_encoder")
+
+    def encode_input_image(self, input_image, end_image, num_frames, height, width, tiled=True, tile_size=(30, 52),
+                           tile_stride=(15, 26)):
+        """WanVideoUnit_ImageEmbedderVAE (wan_video_new.py:704-727) -> y (1, 20, T', h, w) bf16: the 4
+        mask channels (image_mask) over the 16 VAE latents of [image, zeros ... (, end_image)].  A PIL
+        image is resized to (width, height) with PIL's default resample, as the reference does; a uint8
+        (H, W, 3) tensor / array must already be height x width."""
+        from .vae import frames_to_u8, preprocess_video
+        if self.vae is None:
+            raise RuntimeError("input_image encoding requires a loaded Wan2.1 VAE")
+
+        def frame(img, name):
+            if hasattr(img, "resize") and hasattr(img, "convert"):
+                img = img.resize((width, height))
+            elif isinstance(img, torch.Tensor) and img.dim() == 3:
+                img = img[None]
+            u8 = frames_to_u8(img if isinstance(img, torch.Tensor) else [img], self.device)
+            if tuple(u8.shape) != (1, height, width, 3):
+                raise ValueError(f"{name} must be one {height}x{width} RGB image, got {tuple(u8.shape)}")
+            return preprocess_video(u8)
+
+        image = frame(input_image, "input_image")
+        end = None if end_image is None else frame(end_image, "end_image")
+        vae_input = image_vae_input(image, end, num_frames)
+        lat = self.vae.encode(vae_input.to(self.torch_dtype), self.device, tiled=tiled, tile_size=tile_size,
+                              tile_stride=tile_stride)
+        msk = image_mask(num_frames, height // 8, width // 8, end is not None, device=lat.device, dtype=lat.dtype)
+        return torch.cat([msk[None], lat.to(self.torch_dtype)], dim=1).contiguous()
 
     def encode_input_video(self, input_video, input_latents, height, width, num_frames, tiled, tile_size,
                            tile_stride, vace_reference_image=None):

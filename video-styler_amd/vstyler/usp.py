@@ -263,6 +263,7 @@ class UlyssesGroup:
         vl = take(vace_x, "sp_vace") if vace_x is not None else None
         rc2 = RunCtx(B, Sl, rc.grid, rc.rope, rc.ctx, rc.ctx_len, ws, sp=self, token_offset=self.rank * Sl)
         rc2.full_seq = S
+        rc2.img, rc2.img_batch = rc.img, rc.img_batch      # image keys: token-local, replicated
         return xl, vl, rc2
 
     def gather_tokens(self, out, rc):

@@ -42,7 +42,8 @@ int vs_abi_version(void);
 #define VS_OPT_GEMM_KERNEL 1   /* 4: the 4-wave 256x256 kernels (default); 8: the 8-phase ones         */
 #define VS_OPT_GEMM_SPLIT 2    /* 1: split tails (default); 0: whole-tile grids                        */
 #define VS_OPT_QUEUE 3         /* 1: XCD work queues of the persistent GEMMs / self-attention (default; a kind-5 workspace); 0: static lists */
-#define VS_OPT_ATTN_IMPL 4     /* 0: auto (default: 4-wave for >= 16 key tiles); 4 / 8 force a kernel  */
+#define VS_OPT_ATTN_IMPL 4     /* 0: auto (default: 4-wave for >= 4 key tiles); 4 / 8 force a kernel;   */
+                               /* the 4-wave one runs only under attn_mfma=16, attn_nc=1 and a bound kind-4 workspace */
 #define VS_OPT_ATTN_MFMA 5     /* 16 (default) / 32: the 8-wave kernel's MFMA shape                     */
 #define VS_OPT_ATTN_NC 6       /* 1: optimistic softmax + checked redo (default); 0: checked only       */
 #define VS_OPT_ATTN_SPLIT 7    /* 1: split tails (default); 0: whole-item grids                        */

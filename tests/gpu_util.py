@@ -270,3 +270,280 @@ class RowTally:
         print(f"{self.what}: bit-identical share {share:.5f} of {self.total}")
         assert share >= ROW_MIN_IDENTICAL, (self.what, share)
         return share
+
+
+# ------------------------------------------------------------------------------ attention references
+# The contract of vs_attn_fwd (both kernels, every route): Q pre-scaled by c = fp32(scale) * fp32(log2 e)
+# with ONE bf16 rounding, p = exp2(S [- m]) rounded to bf16, fp32 accumulation of P V and of l = sum p,
+# store bf16(acc * (1 / l)).  Two references restate it in float64 (test_attention_exact_gpu.py, the
+# preconditions of both in test_kernel_refs_cpu.py):
+#   * attn_exact_inputs: inputs on which every step but the last is exact in fp32, so the answer is
+#     known to the bit wherever the float64 ratio is not next to a bf16 rounding midpoint;
+#   * attn_random_*: random inputs with a per-element bound derived from the two bf16 roundings.
+ATTN_HD = 128
+ATTN_EXACT_SCALE = torch.tensor(math.log(2.0), dtype=torch.float32).item()      # float32(ln 2)
+ATTN_WINDOW = 8             # fp32 ulps around a bf16 midpoint: device 1/l, the product, a 1-ulp exp2 in l ~ 3.5
+ATTN_MAX_AMBIGUOUS = 0.01   # a condition on the INPUTS (asserted from the reference alone), no tolerance
+ATTN_BOUND = 2.0 ** -8      # |got - o| <= 2^-8 (|o| + A): see attn_within
+ATTN_ROUTES = {"default": {}, "impl8": {"attn_impl": 8}, "nc0": {"attn_nc": 0}, "mfma32": {"attn_mfma": 32}}
+W4_LMIN = 2.0 ** -4         # csrc/attention.h: attn_fwd_w4 sends an item with a row sum below it to the redo
+
+
+def attn_prescale(q, scale):
+    """bf16(fp32(q) * c), c = fp32(scale) * 1.4426950408889634f: the kernels' own product and rounding."""
+    c = torch.tensor(scale, dtype=torch.float32) * torch.tensor(1.4426950408889634, dtype=torch.float32)
+    return (q.float() * c.to(q.device)).to(BF16)
+
+
+def attn_exact_inputs(B, Sq, Skv, H, seed, shared_kv=False, r_rows=None):
+    """q [B*Sq, H*128], k, v [(1 if shared_kv else B)*Skv, H*128] (bf16, CPU) of the exact problem:
+    q: per (row, head) a 1 at a seeded column 0..126 and a seeded integer r in -2..2 at column 127 (a
+       per-row shift that cancels in the ratio); r_rows {row: r} overrides r for that row of every
+       (sample, head);
+    k: columns 0..126 seeded integers -lev, lev 0..3; column 127 = 1  -> every score is an integer;
+    v: zero except where (key + column + 3 head) % 8 == 0, there seeded integers 1..4."""
+    g = torch.Generator().manual_seed(seed)
+    Bk = 1 if shared_kv else B
+    col = torch.randint(0, 127, (B * Sq, H), generator=g)
+    r = torch.randint(-2, 3, (B * Sq, H), generator=g)
+    for row, val in (r_rows or {}).items():
+        r.view(B, Sq, H)[:, row, :] = val
+    q = torch.zeros(B * Sq, H, ATTN_HD)
+    q.scatter_(2, col.unsqueeze(-1), 1.0)
+    q[:, :, 127] = r.float()
+    k = -torch.randint(0, 4, (Bk * Skv, H, ATTN_HD), generator=g).float()
+    k[:, :, 127] = 1.0
+    val = torch.randint(1, 5, (Bk * Skv, H, ATTN_HD), generator=g).float()
+    j = torch.arange(Skv).repeat(Bk).view(-1, 1, 1)
+    h = torch.arange(H).view(1, -1, 1)
+    d = torch.arange(ATTN_HD).view(1, 1, -1)
+    v = torch.where((j + d + 3 * h) % 8 == 0, val, torch.zeros(()))
+    flat = lambda t: t.reshape(t.shape[0], H * ATTN_HD).to(BF16)  # noqa: E731
+    return flat(q), flat(k), flat(v)
+
+
+def attn_ref64(q, k, v, H, B, scale, shared_kv=False, exact=False):
+    """The contract in float64 on the tensors' device, chunked over query rows.  q [B*Sq, >= H*128] rows,
+    k / v [B*Skv or Skv, ...] (views allowed).  Returns a dict: o = sum p v / l and A = sum p |v| / l
+    ([B*Sq, H*128]), l = sum exp2(S) and smin / smax, the extreme scores ([B*Sq, H]), from
+    S = bf16(q c) . k.  exact=True also checks the exact problem's preconditions (the pre-scaling leaves
+    q unchanged; integer scores; every P V and l partial sum, attn_fwd_w4's up to 63 padded keys of
+    weight 1 included, a multiple of the row's smallest p below 2^24 of them) and returns them in `pre`."""
+    dev = q.device
+    Sq, Skv = q.shape[0] // B, k.shape[0] // (1 if shared_kv else B)
+    D = H * ATTN_HD
+    qs = attn_prescale(q[:, :D], scale)
+    pre = {"q_unchanged": same_bits(qs, q[:, :D].contiguous()), "integer": True, "exact": True, "pv_max": 0.0}
+    out = {n: torch.empty(B * Sq, D, dtype=torch.float64, device=dev) for n in ("o", "A")}
+    out.update({n: torch.empty(B * Sq, H, dtype=torch.float64, device=dev) for n in ("l", "smin", "smax")})
+    step = max(1, (1 << 22) // Skv)
+    for b in range(B):
+        kb = 0 if shared_kv else b
+        for h in range(H):
+            cs = slice(h * ATTN_HD, (h + 1) * ATTN_HD)
+            k64 = k[kb * Skv:(kb + 1) * Skv, cs].double()
+            v64 = v[kb * Skv:(kb + 1) * Skv, cs].double()
+            for r0 in range(b * Sq, (b + 1) * Sq, step):
+                rs = slice(r0, min(r0 + step, (b + 1) * Sq))
+                s = qs[rs, cs].double() @ k64.t()
+                m = s.max(dim=1, keepdim=True).values
+                p = torch.exp2(s - m)
+                lr = p.sum(dim=1, keepdim=True)
+                out["o"][rs, cs] = (p @ v64) / lr
+                pav = p @ v64.abs()
+                out["A"][rs, cs] = pav / lr
+                out["l"][rs, h] = (lr * torch.exp2(m)).squeeze(1)
+                out["smax"][rs, h] = m.squeeze(1)
+                smin = s.min(dim=1, keepdim=True).values
+                out["smin"][rs, h] = smin.squeeze(1)
+                if exact:
+                    pre["integer"] = pre["integer"] and bool((s == s.round()).all())
+                    # in units of the row's smallest p (every partial sum is a whole number of them)
+                    units = (pav.max(dim=1, keepdim=True).values * torch.exp2(m) + 64.0) * torch.exp2(-smin)
+                    pre["exact"] = pre["exact"] and bool((units < 2.0 ** 24).all())
+                    pre["pv_max"] = max(pre["pv_max"], (pav * torch.exp2(m)).max().item())
+    out["pre"] = pre
+    return out
+
+
+def attn_exact_ref(q, k, v, H, B, shared_kv=False, window=ATTN_WINDOW):
+    """(ref bf16, ambiguous bool, ref64 dict) of the exact problem at scale float32(ln 2): float64 ->
+    fp32 -> bf16, and the elements within `window` fp32 ulps of a bf16 rounding midpoint."""
+    r = attn_ref64(q, k, v, H, B, ATTN_EXACT_SCALE, shared_kv, exact=True)
+    return r["o"].float().to(BF16), near_bf16_midpoint(r["o"], window), r
+
+
+def attn_exact_preconditions(r, amb, smin=-5, smax=2):
+    """The exact problem's preconditions on a reference (r, amb) of attn_exact_ref; returns the ambiguous
+    share.  Rows with an overridden r (the redo-threshold case) widen the score range: pass it."""
+    pre = r["pre"]
+    assert pre["q_unchanged"], "bf16(q * c) != q at scale float32(ln 2)"
+    assert pre["integer"] and pre["exact"], pre
+    assert pre["pv_max"] < 2.0 ** 19, pre
+    assert r["smin"].min().item() >= smin and r["smax"].max().item() <= smax, (r["smin"].min(), r["smax"].max())
+    share = amb.double().mean().item()
+    assert share <= ATTN_MAX_AMBIGUOUS, share
+    return share
+
+
+def attn_exact_verdict(got, ref, amb, ref64):
+    """The exact bar on one result (got bf16 [rows, H*128]): every element within one bf16 ulp of ref,
+    every non-ambiguous element bit-identical, exact zeros +0.  Returns (ok, text)."""
+    got, ref, amb = got.cpu(), ref.cpu(), amb.cpu()
+    d = (bf16_ord(got) - bf16_ord(ref)).abs()
+    finite = bool(torch.isfinite(got.float()).all())
+    diff = bits(got) != bits(ref)
+    hard = diff & ~amb
+    zeros = ref64.cpu() == 0
+    zero_ok = bool((bits(got)[zeros] == 0).all())
+    text = (f"max ulp {int(d.max())}, differing {int(diff.sum())} ({int(hard.sum())} not ambiguous) of {got.numel()}, "
+            f"ambiguous {int(amb.sum())}, exact zeros {int(zeros.sum())} (+0: {zero_ok}), finite {finite}")
+    return finite and int(d.max()) <= 1 and not bool(hard.any()) and zero_ok, text
+
+
+def attn_midpoint_distance(got, ref, ref64):
+    """For the elements where got != ref by one bf16 ulp: the distance of the float64 value from the
+    bf16 rounding midpoint, in fp32 ulps (the measurement behind ATTN_WINDOW); empty when none differ."""
+    got, ref, x = got.cpu(), ref.cpu(), ref64.cpu()
+    sel = bits(got) != bits(ref)
+    a = x[sel].abs()
+    e = torch.floor(torch.log2(torch.clamp(a, min=2.0 ** -126)))
+    u = a / torch.pow(torch.tensor(2.0, dtype=torch.float64), e - 23)
+    return (torch.remainder(u, 65536.0) - 32768.0).abs()
+
+
+def attn_add_ref(o0, ref, amb, ref64):
+    """vs_attn_fwd_add's o = bf16(o0 + bf16(attention)) from the exact reference: (want, other).  The fp32
+    sum of an integer o0 in -4..4 and a bf16 value is exact (asserted), so the second rounding has one
+    answer; an ambiguous first rounding may land on ref's bf16 neighbour across the midpoint, whose sum
+    is `other` (= want where not ambiguous): a result must equal want or other."""
+    def add(x):
+        s32 = o0.float() + x.float()
+        assert torch.equal(s32.double(), o0.double() + x.double())
+        return s32.to(BF16)
+    o = bf16_ord(ref) + torch.where(ref64 > ref.double(), 1, -1)
+    mag = o.abs()
+    pat = torch.where(o < 0, mag | 0x8000, mag)
+    across = (pat - ((pat & 0x8000) << 1)).to(torch.int16).view(BF16)
+    want = add(ref)
+    return want, torch.where(amb, add(across), want)
+
+
+def attn_random_inputs(B, Sq, Skv, H, seed):
+    """q ~ 2 N(0, 1), k, v ~ N(0, 1) as bf16 [B*S, H*128] (CPU)."""
+    g = torch.Generator().manual_seed(seed)
+    D = H * ATTN_HD
+    return ((2.0 * torch.randn(B * Sq, D, generator=g)).to(BF16), torch.randn(B * Skv, D, generator=g).to(BF16),
+            torch.randn(B * Skv, D, generator=g).to(BF16))
+
+
+def attn_spike_inputs(kind):
+    """The inputs of test_kernels_gpu's test_attention_online_rescale_spike / _overflow_spike /
+    _first_tile_low_scores[late] / _rescale_many, rebuilt: (q, k, v, H, B) as [B*S, H*128] rows."""
+    def rnd(*shape, seed):
+        return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)).to(BF16)
+    if kind == "rescale_spike":
+        S, H = 512, 1
+        q, k, v = rnd(S, 128, seed=30), rnd(S, 128, seed=31), rnd(S, 128, seed=32)
+        q[5] = 4.0
+        k[400] = 4.0
+    elif kind == "overflow_spike":
+        S, H = 512, 1
+        q, k, v = rnd(S, 128, seed=33), rnd(S, 128, seed=34), rnd(S, 128, seed=35)
+        for row, key in ((3, 10), (5, 300), (9, 360), (200, 511)):
+            q[row] = 6.0
+            k[key] = 6.0
+    elif kind in ("low_scores", "low_scores_late"):
+        S, H = 512, 1
+        g = torch.Generator().manual_seed(36)
+        u = torch.ones(128)
+        k = (0.1 * torch.randn(1, S, 128, generator=g) + u).to(BF16)[0]
+        if kind == "low_scores_late":
+            k[64:] = torch.randn(S - 64, 128, generator=g).to(BF16)
+        q = torch.randn(1, S, 128, generator=g).to(BF16)[0]
+        for row in (0, 7, 200, 511):
+            q[row] = (-4.0 * u + 0.01 * torch.randn(128, generator=g)).to(BF16)
+        v = torch.randn(1, S, 128, generator=g).to(BF16)[0]
+    elif kind == "rescale_many":
+        S, H = 2048, 2
+        q, k, v = rnd(1, S, 256, seed=50)[0], rnd(1, S, 256, seed=51)[0], rnd(1, S, 256, seed=52)[0]
+        for key, row, a in ((300, 7, 0.3), (900, 7, 0.5), (1500, 7, 0.8), (130, 40, 0.4), (1999, 300, 0.6),
+                            (64, 1000, 0.35), (1000, 2047, 0.7), (2047, 12, 0.9)):
+            k[key] = (q[row].float() * a).to(BF16)
+    else:
+        raise ValueError(kind)
+    return q, k, v, H, 1
+
+
+def attn_within(got, r):
+    """error / bound per element, bound = 2^-8 (|o| + A) from attn_ref64's dict: half a bf16 ulp on each
+    p moves the numerator by 2^-9 A and the denominator by 2^-9 |o| (relative 2^-9 of l, times o), the
+    output rounding is 2^-9 |o|, and the A term carries about twice the remaining slack for the fp32 sums."""
+    err_ = (got.double().to(r["o"].device) - r["o"]).abs()
+    bound = ATTN_BOUND * (r["o"].abs() + r["A"])
+    return err_ / torch.clamp(bound, min=1e-300)
+
+
+# The GPU cases of test_attention_exact_gpu.py, by name: the arguments of attn_exact_inputs.  One table,
+# so that test_kernel_refs_cpu.py checks the preconditions of exactly the inputs the GPU tests use.
+ATTN_EDGE_SKV_W8 = [1, 7, 31, 32, 33, 63, 64, 65, 129, 192]                       # < 4 key tiles: 8-wave on every route
+ATTN_EDGE_SKV_W4 = [193, 224, 225, 255, 256, 257, 288, 289, 319, 320, 321, 383, 384, 385, 448, 449]   # nkv 4..8
+ATTN_EDGE_SQ = [1, 63, 64, 65, 255, 256, 257]
+ATTN_REDO_ROWS = {17: -10, 290: -11}      # q-block 0 keeps l >= 2^-4 (stays on attn_fwd_w4), q-block 1 falls below
+
+
+def attn_exact_cases():
+    c = {}
+    for skv in ATTN_EDGE_SKV_W8 + ATTN_EDGE_SKV_W4:
+        c[f"edge_skv{skv}"] = dict(B=2, Sq=300, Skv=skv, H=2, seed=1000 + skv)
+    for sq in ATTN_EDGE_SQ:
+        c[f"edge_sq{sq}"] = dict(B=2, Sq=sq, Skv=257, H=2, seed=2000 + sq)
+    c["fused_qkv"] = dict(B=2, Sq=321, Skv=321, H=2, seed=3001)
+    c["shared_kv"] = dict(B=2, Sq=300, Skv=257, H=2, seed=3002, shared_kv=True)
+    c["redo"] = dict(B=2, Sq=300, Skv=193, H=2, seed=3003, r_rows=ATTN_REDO_ROWS)
+    c["switch"] = dict(B=2, Sq=9000, Skv=520, H=4, seed=3004)
+    c["split"] = dict(B=1, Sq=23040, Skv=2079, H=3, seed=3005)
+    c["add_skv257"] = dict(B=2, Sq=300, Skv=257, H=2, seed=3006)
+    c["add_skv449"] = dict(B=2, Sq=300, Skv=449, H=2, seed=3007)
+    return c
+
+
+ATTN_RANDOM_SHAPES = [(2, 300, 77, 2), (2, 300, 300, 2), (2, 300, 449, 2), (1, 1000, 2048, 2)]
+ATTN_SPIKE_KINDS = ["rescale_spike", "overflow_spike", "low_scores", "low_scores_late", "rescale_many"]
+ATTN_BOUND_CASES = ["x".join(map(str, s)) for s in ATTN_RANDOM_SHAPES] + ATTN_SPIKE_KINDS
+
+
+def attn_bound_case(name):
+    """(q, k, v, H, B) of a bound-tier case: "BxSqxSkvxH" random inputs or a spike kind."""
+    if name in ATTN_SPIKE_KINDS:
+        return attn_spike_inputs(name)
+    B, Sq, Skv, H = (int(x) for x in name.split("x"))
+    return (*attn_random_inputs(B, Sq, Skv, H, seed=5000 + Skv), H, B)
+
+
+def attn_add_o0(shape, skv):
+    """vs_attn_fwd_add's prior output: seeded integers in -4..4 (bf16, CPU)."""
+    return torch.randint(-4, 5, tuple(shape), generator=torch.Generator().manual_seed(4000 + skv)).to(BF16)
+
+
+def attn_emulate_fp32(q, k, v, H, B, scale, shared_kv=False, drop_last_key=False, l_add=0.0, truncate_p=False):
+    """The contract evaluated in fp32 on the CPU (optimistic form: p = exp2(S) without a reference max,
+    so for moderate scores only): what a correct kernel computes, for test_kernel_refs_cpu.py to hold
+    the references' bars against -- and, with one of the three arithmetic mutations, what a subtly wrong
+    one does."""
+    Sq, Skv = q.shape[0] // B, k.shape[0] // (1 if shared_kv else B)
+    qs = attn_prescale(q, scale).float()
+    out = torch.empty(B * Sq, H * ATTN_HD, dtype=BF16)
+    n = Skv - 1 if drop_last_key else Skv
+    for b in range(B):
+        kb = 0 if shared_kv else b
+        for h in range(H):
+            cs = slice(h * ATTN_HD, (h + 1) * ATTN_HD)
+            rs = slice(b * Sq, (b + 1) * Sq)
+            p = torch.exp2(qs[rs, cs] @ k[kb * Skv:kb * Skv + n, cs].float().t())
+            if truncate_p:
+                p = (p.view(torch.int32) & -65536).view(torch.float32)
+            p = p.to(BF16).float()
+            lsum = p.sum(dim=1, keepdim=True) + l_add
+            out[rs, cs] = ((p @ v[kb * Skv:kb * Skv + n, cs].float()) * (1.0 / lsum)).to(BF16)
+    return out

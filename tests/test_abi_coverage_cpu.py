@@ -17,7 +17,7 @@ COVERED = {
     "vs_gemm_fp8": ("test_fp8_gpu.py", "test_gemm_fp8_integer_exact", "gemm_fp8("),
     "vs_gemm_fp8_lora": ("test_fp8_lora_gpu.py", "test_gemm_fp8_lora_integer_exact", "gemm_fp8("),
     "vs_gemm_fp8_ws": ("test_fp8_scaled_gpu.py", "test_gemm_fp8_ws_integer_exact", "scale_w"),
-    "vs_attn_fwd": ("test_kernels_gpu.py", "test_attention_key_tile_edges", "K.attention("),
+    "vs_attn_fwd": ("test_attention_exact_gpu.py", "test_attention_exact_key_tile_edges", "K.attention("),
     "vs_layernorm_modulate": ("test_kernels_gpu.py", "test_layernorm_modulate_edges", "K.layernorm_modulate("),
     "vs_layernorm_modulate_fp8": ("test_kernels_gpu.py", "test_layernorm_modulate_fp8_edges",
                                   "K.layernorm_modulate_fp8("),

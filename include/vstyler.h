@@ -393,7 +393,9 @@ int vs_vae_softmax(const float* s, long long ld_s, void* p, long long ld_p, long
  * out[z][r][:c] = softmax(q k^T / sqrt(c)) v over `rows` pixels, with q | k | v the columns [0, c) |
  * [c, 2c) | [2c, 3c) of qkv[z][r] (the to_qkv output, row stride ld_qkv, frame stride qkv_zs); the
  * softmax exact (two passes over K), rounded to bf16 before P.V as vs_vae_softmax; no score
- * buffer.  c % 128 == 0, c <= 384; ld_qkv % 8 == 0, qkv 16-B aligned, ld_o % 4 == 0.
+ * buffer.  c % 128 == 0, c <= 384; ld_qkv % 8 == 0 and qkv_zs % 8 == 0, qkv 16-B aligned (16-B loads
+ * at qkv + z qkv_zs + r ld_qkv); ld_o % 4 == 0 and o_zs % 4 == 0, out 8-B aligned (8-B stores);
+ * anything else is VS_E_INVALID.
  * Replaces AttentionBlock's F.scaled_dot_product_attention (wan_video_vae.py:330-335). */
 int vs_vae_attention(const void* qkv, long long qkv_zs, long long ld_qkv, void* out, long long o_zs,
                      long long ld_o, int nz, int rows, int c, void* stream);

@@ -547,3 +547,315 @@ def attn_emulate_fp32(q, k, v, H, B, scale, shared_kv=False, drop_last_key=False
             lsum = p.sum(dim=1, keepdim=True) + l_add
             out[rs, cs] = ((p @ v[kb * Skv:kb * Skv + n, cs].float()) * (1.0 / lsum)).to(BF16)
     return out
+
+
+# ------------------------------------------------------------------------- VAE conv: the exact problem
+# vs_vae_conv in convolution mode (test_vae_conv_exact_gpu.py; preconditions in test_kernel_refs_cpu.py).
+# x and w in {-1, 0, 1}, bias an integer in -3..3, the residual an integer in -8..8: every fp32 partial
+# sum is an integer far below 2^24, so any summation order gives the same value, and bf16(acc + bias)
+# and bf16(that + res) are exact while both stay within +-256 (asserted from the float64 reference).
+CONV_EXACT_LIMIT = 256.0
+CONV_MIN_NONZERO = 0.5
+
+
+def conv_density(cin):
+    """The share of non-zero entries of x and of w by input width (keeps 27-tap sums within +-256)."""
+    return 1.0 if cin <= 32 else 0.5 if cin <= 96 else 0.35 if cin <= 192 else 0.25
+
+
+def _k3(cin, cout, hw, t, t_lo, res, **kw):
+    return dict(cin=cin, cout=cout, k=(3, 3, 3), pad=(2, 1, 1), t=t, hw=hw, out=(t, *hw), t_lo=t_lo, res=res, **kw)
+
+
+def conv_exact_cases():
+    """name -> geometry.  t / hw: the input's frames and source size; out: (t_out, h_out, w_out); y_t: frames
+    of y the call may address (default t_out; the buffer gets one guard frame more); keep: frames of y the
+    call must not write.  Defaults: n = 2, stride 1, no pad, no up2, t_lo = 0, t_mul = 1, t_add = 0, split = 0,
+    with bias, without residual."""
+    c = {}
+    # k3 causal convs: the launcher each reaches with vae_halo = 1 / 0 is listed in
+    # test_vae_conv_exact_gpu.py's docstring
+    c["k3_32_96_17x33_t4_res"] = _k3(32, 96, (17, 33), 4, 0, True)
+    c["k3_32_96_1x1_t1"] = _k3(32, 96, (1, 1), 1, 0, False)
+    c["k3_96_192_16x32_t4_lo1"] = _k3(96, 192, (16, 32), 4, 1, False)
+    c["k3_96_192_15x31_t4_lo2_res"] = _k3(96, 192, (15, 31), 4, 2, True)
+    c["k3_384_96_16x32_t1_res"] = _k3(384, 96, (16, 32), 1, 0, True)
+    c["k3_32_16_17x33_t4_lo1_res"] = _k3(32, 16, (17, 33), 4, 1, True)
+    c["k3_32_16_15x31_t1"] = _k3(32, 16, (15, 31), 1, 0, False)
+    c["k3_32_3_17x33_t4_lo2"] = _k3(32, 3, (17, 33), 4, 2, False)
+    c["k3_32_3_1x1_t4_res"] = _k3(32, 3, (1, 1), 4, 0, True)
+    c["k3_32_3_16x32_t1"] = _k3(32, 3, (16, 32), 1, 0, False)
+    c["k3_96_64_17x33_t4_lo1_res"] = _k3(96, 64, (17, 33), 4, 1, True)
+    c["k3_96_64_16x32_t1"] = _k3(96, 64, (16, 32), 1, 0, False)
+    c["k3_64_128_15x31_t4"] = _k3(64, 128, (15, 31), 4, 0, False)
+    c["k3_64_128_1x1_t1_res"] = _k3(64, 128, (1, 1), 1, 0, True)
+    c["k3_96_100_17x33_t4_lo2_res"] = _k3(96, 100, (17, 33), 4, 2, True)
+    c["k3_96_100_16x32_t1"] = _k3(96, 100, (16, 32), 1, 0, False)
+    # the same conv writing frames 1.. of a y whose frame 0 must stay (t_add in both epilogues of the halo kernel)
+    c["k3_32_96_17x33_t2_tadd"] = _k3(32, 96, (17, 33), 2, 0, True, t_add=1, y_t=3, keep=(0,))
+    c["k3_32_16_17x33_t2_tadd"] = _k3(32, 16, (17, 33), 2, 0, False, t_add=1, y_t=3, keep=(0,))
+    # Resample upsample2d / 3d: kt = 1 3x3 through the fused nearest-x2 upsample, odd source sizes, 18 x 34
+    # ragged against the halo kernel's 16 x 32 tile
+    c["up2_96_96"] = dict(cin=96, cout=96, k=(1, 3, 3), pad=(0, 1, 1), t=2, hw=(9, 17), out=(2, 18, 34), up2=True, res=True)
+    c["up2_64_64"] = dict(cin=64, cout=64, k=(1, 3, 3), pad=(0, 1, 1), t=2, hw=(9, 17), out=(2, 18, 34), up2=True)
+    # Resample downsample: ZeroPad2d((0, 1, 0, 1)) + 3x3 stride 2 (only the even size reads the zero row / column)
+    for h, w in ((8, 12), (7, 11)):
+        c[f"down_{h}x{w}"] = dict(cin=64, cout=64, k=(1, 3, 3), stride=(1, 2, 2), t=2, hw=(h, w),
+                                  out=(2, (h + 1 - 3) // 2 + 1, (w + 1 - 3) // 2 + 1))
+    # downsample3d's time conv: stride 2 over frames (2j, 2j + 1, 2j + 2) into frames 1.. of y
+    for t in (3, 4, 5):
+        to = (t - 1) // 2
+        c[f"time_down_t{t}"] = dict(cin=64, cout=64, k=(3, 1, 1), stride=(2, 1, 1), t=t, hw=(5, 7), out=(to, 5, 7),
+                                    t_add=1, y_t=1 + to, keep=(0,))
+    # upsample3d's time conv: frames 1.. only (t_lo = 1), channel halves interleaved into frames 2j + 1, 2j + 2
+    for ch in (32, 64):
+        for t in (2, 3):
+            c[f"time_up_c{ch}_t{t}"] = dict(cin=ch, cout=2 * ch, k=(3, 1, 1), pad=(1, 0, 0), t=t, hw=(5, 7),
+                                            out=(t - 1, 5, 7), t_lo=1, t_mul=2, t_add=1, split=ch, y_t=1 + 2 * (t - 1),
+                                            keep=(0,))
+    # AttentionBlock's proj: 1x1x1 with the residual, into a given y
+    c["proj_96"] = dict(cin=96, cout=96, k=(1, 1, 1), t=2, hw=(6, 10), out=(2, 6, 10), res=True)
+    # the load pipeline: nsteps = cin / 32 = 1..7 K-steps (every residue of the three-stage rotation and the
+    # nsteps > 1 / > 2 prologue branches), M = 2 * 10 * 15 = 300 pixels (a ragged 256-pixel tile)
+    for s in range(1, 8):
+        c[f"steps{s}"] = dict(cin=32 * s, cout=96, k=(1, 1, 1), t=1, hw=(10, 15), out=(1, 10, 15), res=s % 2 == 0)
+    return c
+
+
+CONV_STEP_CASES = [f"steps{s}" for s in range(1, 8)]
+CONV_PIPELINES = [(pxb, pre) for pxb in (1, 2) for pre in (1, 2, 3)]
+
+
+def conv_halo_eligible(c):
+    """csrc/vae.hip halo_nb() restated for the cases above: 0 (the per-tap kernel only), or the NB of
+    the patch-resident kernel that vae_halo = 1 selects."""
+    ok = (c["k"][1:] == (3, 3) and c.get("stride", (1, 1, 1)) == (1, 1, 1) and c.get("pad", (0, 0, 0))[1:] == (1, 1)
+          and c.get("split", 0) == 0)
+    return 0 if not ok else 3 if c["cout"] % 96 == 0 else 1 if c["cout"] <= 32 else 0
+
+
+def conv_ldy(c):
+    """cout rounded up to 4 (8 where the halo kernel's NB = 3 epilogue may run) + 8 pad channels."""
+    r = 8 if conv_halo_eligible(c) == 3 else 4
+    return (c["cout"] + r - 1) // r * r + 8
+
+
+_CONV_CACHE = {}
+
+
+def conv_exact_problem(name):
+    """The inputs and the float64 answer of one case, computed once per process and never modified (CPU
+    tensors): x [n, t, h, w, cin] bf16 with NaN in the frames below t_lo, w [cout, cin, kt, kh, kw] bf16,
+    bias bf16 [cout], res (bf16 buffer of y's geometry, NaN outside the written elements, or None), want
+    (bf16 buffer of y's geometry [n, y_t + 1, h_out, w_out, ldy]: the exact answer where the call writes,
+    the sentinel everywhere else), written (bool, same shape) and pre: the reference's own preconditions."""
+    if name in _CONV_CACHE:
+        return _CONV_CACHE[name]
+    import torch.nn.functional as F
+    c = conv_exact_cases()[name]
+    n, cin, cout, (kt, kh, kw) = c.get("n", 2), c["cin"], c["cout"], c["k"]
+    t, (h, w), (to, ho, wo) = c["t"], c["hw"], c["out"]
+    st, pad = c.get("stride", (1, 1, 1)), c.get("pad", (0, 0, 0))
+    t_lo, t_mul, t_add, split = c.get("t_lo", 0), c.get("t_mul", 1), c.get("t_add", 0), c.get("split", 0)
+    g = torch.Generator().manual_seed(sum(ord(ch) * (i + 1) for i, ch in enumerate(name)))
+    d = conv_density(cin)
+
+    def tern(shape):
+        return torch.randint(-1, 2, shape, generator=g).double() * (torch.rand(shape, generator=g) < d)
+    x64 = tern((n, t, h, w, cin))
+    w64 = tern((cout, cin, kt, kh, kw))
+    bias64 = torch.randint(-3, 4, (cout,), generator=g).double()
+    # the reference: X zero outside [t_lo, t_in) x [0, H) x [0, W) of the (upsampled) input, explicitly
+    xz = x64.permute(0, 4, 1, 2, 3).clone()
+    xz[:, :, :t_lo] = 0
+    if c.get("up2"):
+        xz = xz.repeat_interleave(2, dim=3).repeat_interleave(2, dim=4)
+    back = [max(0, (o - 1) * s + k - 1 - p - (i - 1)) for o, s, k, p, i in zip((to, ho, wo), st, (kt, kh, kw), pad, xz.shape[2:])]
+    xz = F.pad(xz, (pad[2], back[2], pad[1], back[1], pad[0], back[0]))
+    acc = F.conv3d(xz, w64, None, stride=st)[:, :, :to, :ho, :wo]
+    assert acc.shape[2:] == (to, ho, wo)
+    r1 = acc + bias64.view(1, -1, 1, 1, 1)
+    y_t, ldy = c.get("y_t", to), conv_ldy(c)
+    shape = (n, y_t + 1, ho, wo, ldy)
+    want = sentinel(shape, device="cpu")
+    written = torch.zeros(shape, dtype=torch.bool)
+    res = sentinel(shape, device="cpu") if c.get("res") else None
+    r2max = 0.0
+    nz = tot = 0
+    for f in range(to):                      # frame placement by t_mul / t_add / split, in plain Python
+        for sub, lo, hi in ((0, 0, split if split > 0 else cout), (1, split, cout if split > 0 else split)):
+            if hi <= lo:
+                continue
+            fr = f * t_mul + t_add + sub
+            assert 0 <= fr < y_t and fr not in c.get("keep", ())
+            v = r1[:, lo:hi, f].permute(0, 2, 3, 1)
+            if res is not None:
+                rr = torch.randint(-8, 9, v.shape, generator=g).double()
+                res[:, fr, :, :, :hi - lo] = rr.to(BF16)
+                v = v + rr
+            assert not bool(written[:, fr, :, :, :hi - lo].any())
+            want[:, fr, :, :, :hi - lo] = v.to(BF16)
+            written[:, fr, :, :, :hi - lo] = True
+            r2max = max(r2max, v.abs().max().item())
+            nz += int((v != 0).sum())
+            tot += v.numel()
+    x = x64.to(BF16)
+    x[:, :t_lo] = float("nan")
+    pre = {"r1_max": r1.abs().max().item(), "r2_max": r2max, "acc_max": acc.abs().max().item(), "nonzero": nz / max(tot, 1)}
+    out = dict(case=c, x=x, w=w64.to(BF16), bias=bias64.to(BF16), res=res, want=want, written=written, pre=pre, ldy=ldy)
+    _CONV_CACHE[name] = out
+    return out
+
+
+def conv_exact_preconditions(p):
+    """From the float64 reference alone: bf16(acc + bias) and bf16(that + res) exact (integers within
+    +-256), and at least half of the outputs non-zero."""
+    pre = p["pre"]
+    assert pre["r1_max"] <= CONV_EXACT_LIMIT and pre["r2_max"] <= CONV_EXACT_LIMIT, pre
+    assert pre["nonzero"] >= CONV_MIN_NONZERO, pre
+    return pre
+
+
+# ---------------------------------------------------------------------- VAE attention (vs_vae_attention)
+# The contract of csrc/vae_attention.hip: s = fp32(q . k) * sc, sc = fp32(log2 e) / sqrtf(C); two passes,
+# P = bf16(exp2(s - m) * (1 / l)), fp32 accumulation of P V, bf16 output.  Two references
+# (test_vae_attention_exact_gpu.py, preconditions in test_kernel_refs_cpu.py):
+#   * "tied groups": every key has a group id, every query selects one group; Q and K carry the id's
+#     bits as +-a over all C dimensions (dimension d carries bit d % VATT_NB with a seeded sign on both).
+#     A tied key's score exceeds every other key's by >= VATT_MIN_GAP in the exp2 domain, so exp2 of
+#     every other key is exactly 0, of a tied key exactly 1, every rescale factor 0 or 1, the row sum
+#     the group size g, P = bf16(fl32(1 / g)); V holds integers in -8..8, so p * sum_{j in G} V_j is
+#     exact in fp32 in any order: the answer is known to the bit, with no ambiguous set;
+#   * random inputs with the per-element bound 2^-8 (|o| + A), A = sum p |v| (vatt_within).
+VATT_ROWS = [1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 257]
+VATT_C = [128, 256, 384]
+VATT_G = [1, 2, 3, 5, 7, 32, "rows"]
+VATT_NZ = 2
+VATT_AMP = 16.0
+VATT_NB = 10                # id bits: 258 groups at most; 10 does not divide the 8-element chunks
+VATT_MIN_GAP = 160.0        # exp2(-160) is below the smallest fp32 denormal
+VATT_WINDOW = 8             # fp32 ulps between fl32(1 / g) and a bf16 midpoint: the device's 1 / l may be 1 ulp off
+VATT_BOUND = 2.0 ** -8
+# test_vae_attention_vs_float64's random cases without the 6240-row one, plus qscale 16: (c, rows, nz, ld_pad, qscale)
+VATT_BOUND_CASES = [(384, 100, 3, 0, 1.0), (384, 33, 2, 64, 4.0), (384, 1, 2, 0, 1.0), (256, 31, 2, 8, 1.0),
+                    (128, 1000, 2, 0, 1.0), (128, 257, 1, 0, 16.0), (384, 100, 3, 0, 16.0)]
+
+
+def vatt_sc(c):
+    """The kernel's score scale: fp32(log2 e) / sqrtf(C), in fp32."""
+    return (torch.tensor(1.4426950408889634, dtype=torch.float32) / torch.sqrt(torch.tensor(float(c), dtype=torch.float32))).item()
+
+
+def vatt_exact_inputs(rows, c, g, nz=VATT_NZ):
+    """qkv [nz, rows, 3c] bf16 (CPU) of the tied-groups problem with group size g ("rows": Q = 0, every
+    key ties).  g < rows: G = rows // g groups of exactly g keys, key j in group j % G (members straddle
+    every key-tile boundary), the rows - G g keys left over a last, smaller group; every query selects a
+    seeded group."""
+    gen = torch.Generator().manual_seed(rows * 1009 + c * 7 + (0 if g == "rows" else g))
+    every = g == "rows" or g >= rows
+    gsz = 7 if every else g
+    G = max(1, rows // gsz)
+    j = torch.arange(rows)
+    gid = torch.where(j < G * gsz, j % G, torch.full_like(j, G))
+    ngroups = int(gid.max()) + 1
+    assert ngroups <= 2 ** VATT_NB
+    d = torch.arange(c)
+    sigma = torch.randint(0, 2, (c,), generator=gen).double() * 2 - 1
+
+    def carry(ids):
+        bit = (ids.view(-1, 1) >> (d % VATT_NB).view(1, -1)) & 1
+        return VATT_AMP * sigma.view(1, -1) * (2.0 * bit.double() - 1)
+    qkv = torch.empty(nz, rows, 3 * c, dtype=torch.float64)
+    for z in range(nz):
+        sel = torch.randint(0, ngroups, (rows,), generator=gen)
+        qkv[z, :, :c] = 0.0 if every else carry(sel)
+        qkv[z, :, c:2 * c] = carry(gid)
+        qkv[z, :, 2 * c:] = torch.randint(-8, 9, (rows, c), generator=gen).double()
+    return qkv.to(BF16)
+
+
+def vatt_exact_ref(qkv, c):
+    """(ref bf16 [nz, rows, c], pre) from float64 alone.  pre: min_gap (the smallest gap, times sc, between
+    a query's top score and any other key; inf when every key ties), sizes (the tie counts that occur),
+    midpoint_ok (fl32(1 / g) >= VATT_WINDOW fp32 ulps from a bf16 midpoint for each), exact (p * S fits fp32)."""
+    q, k, v = (qkv[..., i * c:(i + 1) * c].double() for i in range(3))
+    s = q @ k.transpose(-1, -2)
+    top = s.max(dim=-1, keepdim=True).values
+    tie = s == top
+    others = torch.where(tie, torch.full_like(s, -float("inf")), s).max(dim=-1).values
+    gap = (top.squeeze(-1) - others) * vatt_sc(c)
+    cnt = tie.sum(dim=-1, keepdim=True).double()
+    inv = 1.0 / cnt
+    p = inv.float().to(BF16).double()                        # bf16(fl32(1 / g))
+    S = tie.double() @ v
+    o = p * S
+    pre = {"min_gap": gap.min().item(), "sizes": sorted(int(x) for x in cnt.unique()),
+           "midpoint_ok": not bool(near_bf16_midpoint(inv, VATT_WINDOW).any()),
+           "exact": bool((o.float().double() == o).all()) and bool((s.float().double() == s).all()),
+           "nonzero": (o != 0).double().mean().item()}
+    return o.float().to(BF16), pre
+
+
+def vatt_exact_preconditions(pre, rows, g):
+    assert pre["min_gap"] >= VATT_MIN_GAP and pre["midpoint_ok"] and pre["exact"], pre
+    if g == "rows" or g >= rows:
+        assert pre["sizes"] == [rows], pre
+    else:
+        assert set(pre["sizes"]) <= {g, rows % g} and g in pre["sizes"], pre
+
+
+def vatt_buffers(qkv, c, ld_pad=8, ldo_pad=4, device="cuda"):
+    """The guarded layout of one call: qkv rows of 3c + ld_pad columns with NaN in the pad columns and one
+    NaN guard row after each frame; out a sentinel buffer [nz + 1, rows + 1, c + ldo_pad] (pad columns, one
+    guard row per frame, one guard frame behind the last).  Returns (qbuf, out, the call's arguments after
+    the pointers: qkv_zs, ld_qkv, o_zs, ld_o)."""
+    nz, rows, _ = qkv.shape
+    ld, ldo = 3 * c + ld_pad, c + ldo_pad
+    qbuf = sentinel((nz, rows + 1, ld), device="cpu")
+    qbuf[:, :rows, :3 * c] = qkv
+    return qbuf.to(device), sentinel((nz + 1, rows + 1, ldo), device=device), ((rows + 1) * ld, ld, (rows + 1) * ldo, ldo)
+
+
+def vatt_guards_untouched(out, rows, c):
+    """Pad columns, every frame's guard row and the guard frame still hold the sentinel."""
+    return untouched(out[..., c:]) and untouched(out[:, rows]) and untouched(out[-1])
+
+
+def vatt_random_inputs(c, rows, nz, qscale):
+    """test_vae_attention_vs_float64's inputs (N(0, 1), q scaled by qscale), seeded on the CPU."""
+    g = torch.Generator().manual_seed(c + rows + int(qscale))
+    x = torch.randn((nz, rows, 3 * c), generator=g)
+    x[..., :c] *= qscale
+    return x.to(BF16)
+
+
+def vatt_ref64(qkv, c):
+    """(o, A) in float64: o = softmax(q k^T / sqrt(c)) v, A = sum p |v|."""
+    q, k, v = (qkv[..., i * c:(i + 1) * c].double() for i in range(3))
+    p = torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(c), dim=-1)
+    return p @ v, p @ v.abs()
+
+
+def vatt_within(got, o, A):
+    """error / bound per element, bound = 2^-8 (|o| + A): half a bf16 ulp on each p moves the sum by at most
+    2^-9 A, the output rounding by 2^-9 |o|; the rest is slack for the fp32 sums and the 1 / l reciprocal."""
+    return (got.double().cpu() - o).abs() / torch.clamp(VATT_BOUND * (o.abs() + A), min=1e-300)
+
+
+def vatt_emulate_fp32(qkv, c, twice_last=False, drop_key=None, shift_v=False):
+    """The two-pass kernel in fp32 on the CPU, its bf16 P included: s = fl32(q . k) * sc, m = row max,
+    l = sum exp2(s - m), P = bf16(exp2(s - m) * (1 / l)), out = bf16(P V).  Mutations: the last key counted
+    twice, key drop_key left out, V rows shifted by one (key j weighted onto V[j + 1], cyclically)."""
+    q, k, v = (qkv[..., i * c:(i + 1) * c].float() for i in range(3))
+    if twice_last:
+        k, v = torch.cat([k, k[:, -1:]], dim=1), torch.cat([v, v[:, -1:]], dim=1)
+    if drop_key is not None:
+        keep = [j for j in range(k.shape[1]) if j != drop_key]
+        k, v = k[:, keep], v[:, keep]
+    if shift_v:
+        v = torch.roll(v, -1, dims=1)
+    s = (q @ k.transpose(-1, -2)) * torch.tensor(vatt_sc(c), dtype=torch.float32)
+    m = s.max(dim=-1, keepdim=True).values
+    e = torch.exp2(s - m)
+    p = (e * (1.0 / e.sum(dim=-1, keepdim=True))).to(BF16).float()
+    return (p @ v).to(BF16)

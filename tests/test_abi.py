@@ -79,6 +79,9 @@ def test_invalid_arguments_rejected_before_launch():
     assert lib.vs_vae_attention(fake, 64 * 300, 300, fake, 64 * 128, 128, 1, 64, 128, None) == 1
     assert lib.vs_vae_attention(fake + 8, 64 * 384, 384, fake, 64 * 128, 128, 1, 64, 128, None) == 1
     assert lib.vs_vae_attention(fake, 63 * 384, 384, fake, 64 * 128, 128, 1, 64, 128, None) == 1
+    # frame strides: 16-B loads at qkv + z qkv_zs, 8-B stores at out + z o_zs (both long enough, misaligned)
+    assert lib.vs_vae_attention(fake, 64 * 384 + 4, 384, fake, 64 * 128, 128, 2, 64, 128, None) == 1
+    assert lib.vs_vae_attention(fake, 64 * 384 + 8, 384, fake, 64 * 128 + 2, 128, 2, 64, 128, None) == 1
     # Ulysses permute: columns not a multiple of 8
     assert lib.vs_ulysses_permute(fake, fake, 1, 4, 2, 12, 24, 48, 0, None) == 1
     # SP collectives: argument checks come before RCCL is opened or a device is touched
@@ -166,6 +169,38 @@ def test_gemm_split_plan_host_only():
         if ntail:
             assert pk % 32 == 0 and (ks - 1) * pk < args[2] <= ks * pk
     assert lib.vs_gemm_split_plan(64, 64, 100, 256, out) == 1
+
+
+def test_gemm_split_plan_no_short_piece():
+    """Every split plan over K = 1024..16384 (steps of 64), one to two rounds of tiles, on 8 / 64 / 256 /
+    304 CUs: the pieces cover K, stay within the 512-piece workspace and 512 elements or more each, and
+    the LAST piece holds at least three 64-wide K-tiles.  The 4-wave kernel's persistent blocks take
+    pieces from the piece pool as ordinary work items, and the tile-id hand-off of that walk needs three
+    K-tiles per item (gemm.hip, the schedule's comment): a shorter last piece followed by another item
+    in the same block made that item compute on the wrong K-tile.  Which block takes which piece
+    depends on timing, so the invariant is the plan's (K = 4160 with a 32-tile tail once planned
+    8 x 576, a last piece of 128)."""
+    from vstyler import _lib
+    lib = _lib.load()
+    out = (ctypes.c_int * 4)()
+    nsplit = 0
+    assert lib.vs_gemm_split_plan(256 * 288, 256, 4160, 256, out) == 0 and tuple(out) == (256, 32, 7, 640)
+    for cus in (8, 64, 256, 304):
+        for ntiles in range(cus + 1, 2 * cus):
+            for k in range(1024, 16384 + 1, 64):
+                assert lib.vs_gemm_split_plan(256 * ntiles, 256, k, cus, out) == 0
+                nmain, ntail, ks, pk = out
+                what = (cus, ntiles, k, tuple(out))
+                assert nmain + ntail == ntiles, what
+                if not ntail:
+                    assert (ks, pk) == (1, 0), what
+                    continue
+                nsplit += 1
+                assert ntail == ntiles % cus and ks >= 2, what
+                assert pk % 64 == 0 and (ks - 1) * pk < k <= ks * pk, what
+                assert ntail * ks <= 512 and pk >= 512, what
+                assert k - (ks - 1) * pk >= 192, what
+    assert nsplit > 10000
 
 
 def test_gemm_route_is_fused_everywhere():

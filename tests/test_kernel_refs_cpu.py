@@ -174,3 +174,143 @@ def test_attention_bound_is_met_by_fp32():
         q, k, v, H, B = U.attn_bound_case(name)
         r = U.attn_ref64(q, k, v, H, B, 128 ** -0.5)
         assert bool(torch.isfinite(r["o"]).all()) and bool(torch.isfinite(r["A"]).all())
+
+
+# ------------------------------------------------------------------------------ VAE conv, exact problem
+def test_conv_exact_preconditions_every_gpu_case():
+    """Every case of test_vae_conv_exact_gpu.py, from the float64 reference alone: bf16(acc + bias) and
+    bf16(that + res) are integers within +-256 (exact in bf16, every fp32 partial sum exact in any
+    order), >= half of the outputs non-zero; the buffers have the guards the GPU test relies on (pad
+    channels, a guard frame, the kept frames, NaN below t_lo and around the residual); the case list
+    holds every value the halo kernel and each launcher must see."""
+    cases = U.conv_exact_cases()
+    for name, c in cases.items():
+        p = U.conv_exact_problem(name)
+        pre = U.conv_exact_preconditions(p)
+        print(f"conv exact {name}: max |acc + bias| {pre['r1_max']:.0f}, + res {pre['r2_max']:.0f}, non-zero {pre['nonzero']:.3f}")
+        want, written, x = p["want"], p["written"], p["x"]
+        cout = c["split"] if c.get("split") else c["cout"]
+        assert want.shape[-1] == p["ldy"] >= cout + 8 and p["ldy"] % (8 if U.conv_halo_eligible(c) == 3 else 4) == 0
+        assert not bool(written[..., cout:].any()) and not bool(written[:, -1].any())
+        assert all(not bool(written[:, f].any()) for f in c.get("keep", ()))
+        assert bool(written[:, :c.get("y_t", c["out"][0]), :, :, :cout].any())
+        assert U.untouched(want[~written]) and bool(torch.isfinite(want[written].float()).all())
+        assert bool((want[written].double().abs() <= U.CONV_EXACT_LIMIT).all())
+        t_lo = c.get("t_lo", 0)
+        assert bool(torch.isnan(x[:, :t_lo].float()).all()) and bool(torch.isfinite(x[:, t_lo:].float()).all())
+        assert set(x[:, t_lo:].double().unique().tolist()) <= {-1.0, 0.0, 1.0}
+        assert set(p["w"].double().unique().tolist()) <= {-1.0, 0.0, 1.0}
+        if p["res"] is not None:
+            assert U.untouched(p["res"][~written]) and int(p["res"][written].double().abs().max()) == 8
+        assert x.numel() * 2 < 2 ** 20 * 4 and want.numel() * 2 < 2 ** 20 * 2        # a few hundred KB each
+    # the k3 list: every value on each kernel it can reach
+    k3 = {n: c for n, c in cases.items() if n.startswith("k3_") and "t_add" not in c}
+    for nb, pairs in ((3, {(32, 96), (96, 192), (384, 96)}), (1, {(32, 16), (32, 3)}), (0, {(96, 64), (64, 128), (96, 100)})):
+        sel = [c for c in k3.values() if U.conv_halo_eligible(c) == nb]
+        assert {(c["cin"], c["cout"]) for c in sel} == pairs
+        assert {c["t"] for c in sel} == {1, 4} and {c["res"] for c in sel} == {False, True}
+        assert {c["hw"] for c in sel} == {(1, 1), (16, 32), (17, 33), (15, 31)}
+        assert {c["t_lo"] for c in sel} == {0, 1, 2}
+    for pair in ((96, 64), (64, 128), (96, 100)):
+        assert {c["res"] for c in k3.values() if (c["cin"], c["cout"]) == pair} == {False, True}
+    assert [cases[n]["cin"] // 32 for n in U.CONV_STEP_CASES] == list(range(1, 8))
+    assert len(U.CONV_PIPELINES) == 6
+
+
+def test_conv_exact_bar_has_teeth():
+    """The reference against itself under the mistakes a gather can make: the first input column read as
+    zero, frames below t_lo read, t_add ignored -- each changes the expected buffer (so the bitwise bar
+    separates them), from the reference alone."""
+    import torch.nn.functional as F
+    p = U.conv_exact_problem("k3_96_192_15x31_t4_lo2_res")
+    c = p["case"]
+    x = p["x"].double().permute(0, 4, 1, 2, 3)
+    w = p["w"].double()
+    n_t = c["t"]
+
+    def conv_of(xx, left):
+        return F.conv3d(F.pad(xx, (left, 2 - left, 1, 1, 2, 0)), w)[:, :, :n_t]
+    base = conv_of(torch.nan_to_num(x, nan=0.0), 1)
+    live = p["want"][:, :n_t, :, :, :c["cout"]].double().permute(0, 4, 1, 2, 3)
+    resid = p["res"][:, :n_t, :, :, :c["cout"]].double().permute(0, 4, 1, 2, 3)
+    assert torch.equal(base + p["bias"].double().view(1, -1, 1, 1, 1) + resid, live)      # the restated reference
+    col0 = torch.nan_to_num(x, nan=0.0)
+    col0[..., 0] = 0                                                                     # xi >= 0 -> xi >= 1
+    changed = (conv_of(col0, 1) != base)[:, :, c["t_lo"]:]
+    assert changed[..., :2].double().mean().item() > 0.5 and not bool(changed[..., 2:].any())
+    unmasked = conv_of(torch.nan_to_num(x, nan=1.0), 1)                                  # the t_lo predicate dropped
+    assert bool((unmasked != base)[:, :, :c["t_lo"] + 2].any())
+    q = U.conv_exact_problem("k3_32_96_17x33_t2_tadd")
+    assert U.untouched(q["want"][:, 0]) and not U.untouched(q["want"][:, 1, :, :, :96])  # t_add ignored lands in frame 0
+
+
+# ------------------------------------------------------------------------------ VAE attention references
+def test_vae_attention_exact_preconditions_every_gpu_case():
+    """Every (rows, C, g) of test_vae_attention_exact_gpu.py from the float64 scores alone: the gap to
+    every non-tied key, times sc, >= 160; the tie counts are the group sizes; fl32(1 / g) >= 8 fp32 ulps
+    from a bf16 midpoint; p * S exact in fp32."""
+    worst = float("inf")
+    sizes = set()
+    for c in U.VATT_C:
+        for rows in U.VATT_ROWS:
+            for g in U.VATT_G:
+                if g != "rows" and g >= rows:
+                    continue
+                qkv = U.vatt_exact_inputs(rows, c, g)
+                ref, pre = U.vatt_exact_ref(qkv, c)
+                U.vatt_exact_preconditions(pre, rows, g)
+                assert bool(torch.isfinite(ref.float()).all())
+                if rows > 1:
+                    assert pre["nonzero"] > 0.5, (c, rows, g, pre)
+                worst = min(worst, pre["min_gap"])
+                sizes |= set(pre["sizes"])
+        print(f"vae attention exact C {c}: smallest gap x sc so far {worst:.1f}")
+    assert sizes >= {1, 2, 3, 5, 7, 32} | set(U.VATT_ROWS)
+    # the closest any 1 / g comes to a bf16 midpoint, in fp32 ulps
+    inv = 1.0 / torch.tensor(sorted(sizes), dtype=torch.float64)
+    u = inv / torch.pow(torch.tensor(2.0, dtype=torch.float64), torch.floor(torch.log2(inv)) - 23)
+    dist = (torch.remainder(u, 65536.0) - 32768.0).abs()
+    print(f"vae attention exact: group sizes {sorted(sizes)}, closest 1 / g to a bf16 midpoint: "
+          f"1 / {sorted(sizes)[int(dist.argmin())]} at {dist.min().item():.0f} fp32 ulps")
+    assert dist.min().item() >= U.VATT_WINDOW
+
+
+def test_vae_attention_bars_are_met_by_fp32_and_have_teeth():
+    """The two-pass kernel emulated in fp32 (bf16 P included) meets the exact bar on every exact case and
+    the derived bound on every bound case; with the last key counted twice, one key dropped, or the V rows
+    shifted by one it misses the exact bar on every shape of two rows or more (the g = rows case counts
+    keys) and the bound on the cases named below."""
+    muts = {"twice_last": dict(twice_last=True), "drop_key": dict(drop_key=0), "shift_v": dict(shift_v=True)}
+    for c in U.VATT_C:
+        for rows in U.VATT_ROWS:
+            caught = {m: False for m in muts}
+            for g in U.VATT_G:
+                if g != "rows" and g >= rows:
+                    continue
+                qkv = U.vatt_exact_inputs(rows, c, g)
+                ref, _ = U.vatt_exact_ref(qkv, c)
+                assert U.same_bits(U.vatt_emulate_fp32(qkv, c), ref), (c, rows, g)
+                for m, kw in muts.items():
+                    if rows > 1 and not U.same_bits(U.vatt_emulate_fp32(qkv, c, **kw), ref):
+                        caught[m] = True
+                if g == "rows" and rows > 1:         # the key count itself
+                    for m in ("twice_last", "drop_key"):
+                        assert not U.same_bits(U.vatt_emulate_fp32(qkv, c, **muts[m]), ref), (c, rows, m)
+            assert rows == 1 or all(caught.values()), (c, rows, caught)
+    failed = {m: [] for m in muts}
+    for c, rows, nz, ld_pad, qscale in U.VATT_BOUND_CASES:
+        qkv = U.vatt_random_inputs(c, rows, nz, qscale)
+        o, A = U.vatt_ref64(qkv, c)
+        assert bool(torch.isfinite(o).all()) and bool((A >= o.abs() * (1 - 1e-12)).all())
+        w = U.vatt_within(U.vatt_emulate_fp32(qkv, c), o, A).max().item()
+        line = f"vae attention bound C {c} rows {rows} qscale {qscale}: fp32 emulation worst error / bound {w:.3f}"
+        assert w <= 1.0, line
+        for m, kw in muts.items():
+            if rows > 1:
+                wm = U.vatt_within(U.vatt_emulate_fp32(qkv, c, **kw), o, A).max().item()
+                line += f", {m} {wm:.2f}"
+                if wm > 1.0:
+                    failed[m].append((c, rows, qscale))
+        print(line)
+    for m in muts:
+        assert len(failed[m]) == sum(1 for case in U.VATT_BOUND_CASES if case[1] > 1), (m, failed[m])

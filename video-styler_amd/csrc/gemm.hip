@@ -834,11 +834,14 @@ static_assert(4 * W4_ROWB == 0x1080, "the 4w kernel's M0 step");
 // epilogue's start and its value used at the end, under the stores) -- the second tile's under the
 // prologue's DMAs -- writes it to an LDS word, and every wave reads that word in tile k+1's first
 // K-tile behind a barrier, before the DMA cursor crosses into tile k+2 at the end of K-tile nt - 3
-// (nt >= 3, host-checked).  The last
-// persistent block to finish (exit count q[9]) zeroes the queue words, so every launch finds them
+// (so every work item a block walks needs nt >= 3: for whole tiles w4_sched checks k / 64 on the
+// host; a split-tail K piece is an item like any other, and plan_ksplit / plan_ksplit_held never
+// plan a piece, the last one included, below MIN_PIECE_STEPS = 3 K-tiles).  After the whole tiles
+// the blocks take the launch's split-tail pieces from the piece pool (head q[9], r6).  The last
+// persistent block to finish (exit count q[10]) zeroes the queue words, so every launch finds them
 // zero (workspace kind 5: bound zeroed, one per stream, so graph replays and concurrent streams are
-// safe).  Without a bound queue the same walk runs the static list and the nrem whole tiles get
-// blocks of their own.  The blocks after those run the split-tail K pieces of the last tiles.
+// safe).  Without a bound queue the same walk runs the static list, the nrem whole tiles get
+// blocks of their own, and the blocks after those run the split-tail K pieces of the last tiles.
 // ---------------------------------------------------------------------------------------------
 constexpr int WQ_LINE = VS_Q_LINE;            // queue words 128 B apart (a line each, common.h)
 constexpr int WQ_BYTES = 11 * WQ_LINE * 4;    // 8 XCD heads, the remainder head, the piece head, the exit count
@@ -2129,6 +2132,16 @@ bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0;
 constexpr int MAX_SPLIT_PIECES = 512;        // 512 x 256 KB fp32 partial tiles
 struct KSplit { int nmain = 0, ntail = 0, ksplit = 1, piece_k = 0; };
 
+// A work item of a persistent 4-wave block needs >= 3 K-tiles (the tile-id hand-off, see the
+// schedule's comment), and since r6 the piece pool hands K pieces to those blocks as ordinary items.
+// ceil(nh / f) steps per piece can leave a last piece of 1 or 2 (nh = 65, f = 8: 7 x 9 + 2), so no
+// plan takes such a factor: every piece of every plan has >= MIN_PIECE_STEPS steps.
+constexpr int MIN_PIECE_STEPS = 3;
+static int last_piece_steps(int nh, int f) {
+    const int piece_h = (nh + f - 1) / f;
+    return nh - ((nh + piece_h - 1) / piece_h - 1) * piece_h;
+}
+
 KSplit plan_ksplit(int ntiles, int nh, int cus, int step = 64) {
     // Cost model in microseconds, calibrated on MI355X (tests/probes/split_ab.py): a whole tile
     // takes t = K * 0.029 us at ~1150 TF/s; a round of pieces costs t/f plus ~18 us (prologue and
@@ -2143,6 +2156,7 @@ KSplit plan_ksplit(int ntiles, int nh, int cus, int step = 64) {
     double best = 0.85 * t;
     int bf = 1;
     for (int f = 2; f <= 16 && tail * f <= MAX_SPLIT_PIECES && nh * step / f >= 512; ++f) {
+        if (last_piece_steps(nh, f) < MIN_PIECE_STEPS) continue;
         const int rounds = (tail * f + cus - 1) / cus;
         const double cost = rounds * (t / f + 18.0) + 5.0 + 0.065 * tail * f;
         if (cost < best) { best = cost; bf = f; }
@@ -2169,7 +2183,7 @@ KSplit plan_ksplit_held(int ntiles, int nh, int cus, int step) {
     const int tail = ntiles % cus + R * (cus / 16);
     int f = 0;
     for (int c = 4; c >= 2 && !f; --c)
-        if (tail * c <= MAX_SPLIT_PIECES && nh * step / c >= 512) f = c;
+        if (tail * c <= MAX_SPLIT_PIECES && nh * step / c >= 512 && last_piece_steps(nh, c) >= MIN_PIECE_STEPS) f = c;
     if (!f) return p;
     const int piece_h = (nh + f - 1) / f;
     p.ntail = tail;
@@ -2194,7 +2208,8 @@ KSplit plan_ksplit_held(int ntiles, int nh, int cus, int step) {
 static bool use_4w() { return vs_opt(VS_OPT_GEMM_KERNEL) == 4; }
 
 // the schedule of a 4-wave launch (W4Sched): one persistent block per CU when the main tiles fill
-// every CU and a tile has >= 3 K-tiles (the tile-id hand-off, see the schedule's comment), fed by the
+// every CU and a whole tile has >= 3 K-tiles (the tile-id hand-off, see the schedule's comment; nt
+// here is k / 64, the pieces' own >= 3 K-tiles is the plan's invariant, MIN_PIECE_STEPS), fed by the
 // XCD tile queues when the stream has a queue workspace (kind 5) bound (VS_OPT_QUEUE 0: the
 // static lists)
 // npiece: the launch's split-tail pieces, taken by the persistent blocks from the queue's piece pool

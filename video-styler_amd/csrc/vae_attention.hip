@@ -263,6 +263,8 @@ extern "C" int vs_vae_attention(const void* qkv, long long qkv_zs, long long ld_
         ld_qkv % 8 || ld_o % 4 || qkv_zs < (long long)rows * ld_qkv || o_zs < (long long)rows * ld_o)
         return VS_E_INVALID;
     if ((uintptr_t)qkv & 15 || (uintptr_t)out & 7) return VS_E_INVALID;
+    // frame z starts at qkv + z qkv_zs (16-B loads) and out + z o_zs (8-B stores)
+    if (qkv_zs % 8 || o_zs % 4) return VS_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     switch (c / 32) {
         case 4: return launch_vae_attn<4>(qkv, qkv_zs, ld_qkv, out, o_zs, ld_o, nz, rows, st);

@@ -1,4 +1,5 @@
-"""ctypes binding of libvstyler.so (the C ABI declared in include/vstyler.h and vstyler_image.h).
+"""ctypes binding of libvstyler.so (the C ABI declared in include/vstyler.h, vstyler_image.h and
+vstyler_clip.h).
 
 The product path has no CPU fallback: if the library is missing every op raises.
 """
@@ -124,6 +125,10 @@ SIGNATURES_IMAGE = {
     "vs_attn_fwd_add": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _LL, _LL, _LL, _LL, _LL, _LL, _LL, _LL,
                         _F, _P],
 }
+# the CLIP image encoder's entry (include/vstyler_clip.h): a third table
+SIGNATURES_CLIP = {
+    "vs_clip_preprocess": [_P, _LL, _LL, _LL, _P, _LL, _I, _I, _I, _I, _P],
+}
 _RESTYPES = {"vs_strerror": ctypes.c_char_p, "vs_split_workspace_bytes": ctypes.c_longlong,
              "vs_sp_last_error": ctypes.c_char_p}
 
@@ -139,7 +144,7 @@ def load():
                 f"libvstyler.so not found at {LIB_PATH}: build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or make -C video-styler_amd/csrc)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_IMAGE.items()):
+        for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_IMAGE.items()) + list(SIGNATURES_CLIP.items()):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, ctypes.c_int)

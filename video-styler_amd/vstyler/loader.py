@@ -287,6 +287,28 @@ def build_text_encoder(state_dict, device):
     return WanTextEncoder(device=device, **cfg).load_state_dict(state_dict)
 
 
+CLIP_HASH = "5941c53e207d62f20f9025686193c40b"   # configs/model_config.py:162 (WanImageEncoder)
+
+
+def build_image_encoder(state_dict, device):
+    """WanImageEncoder (vstyler.clip) from models_clip_open-clip-xlm-roberta-large-vit-huge-14.pth: the
+    reference's key hash gives the ViT-H/14 defaults; any other key set that holds the visual tower
+    (visual.transformer.0.attn.to_qkv.weight, with or without the "model." prefix: other widths, the tiny
+    test checkpoints) gets its config from the shapes.  None when the layout is not that tower's."""
+    from .clip import WanImageEncoder, config_from_shapes
+    if hash_state_dict_keys(state_dict) == CLIP_HASH:
+        cfg = {}
+    else:
+        sd = {(k[len("model."):] if k.startswith("model.") else k): v for k, v in state_dict.items()
+              if isinstance(k, str)}
+        if "visual.transformer.0.attn.to_qkv.weight" not in sd:
+            return None
+        cfg = config_from_shapes(sd)
+        if cfg is None:
+            return None
+    return WanImageEncoder(device=device, **cfg).load_state_dict(state_dict, strict=False)
+
+
 def _check_experts(dits):
     """The two experts of one pipeline share the Workspace and every launch shape."""
     if len(dits) == 2:
@@ -297,7 +319,8 @@ def _check_experts(dits):
 
 
 def load_models(paths, device="cuda", fp8_weights="fold"):
-    """Returns {'wan_video_dit': WanModel, 'wan_video_vace': VaceWanModel, ...} for the files given.
+    """Returns {'wan_video_dit': WanModel, 'wan_video_vace': VaceWanModel, ...} for the files given
+    ('wan_video_vae', 'wan_video_text_encoder' and 'wan_video_image_encoder' for those checkpoints).
     fp8_weights: "fold" -- e4m3 tensors become bf16 weights (upcast times scale_weight: normalize_keys)
     and nothing else; "keep" -- the same bf16 model (LoRA merge, hot-load and the bf16 layers work
     unchanged), whose block Linears additionally run the file's e4m3 bytes and scales on the fp8 GEMMs
@@ -326,6 +349,10 @@ def load_models(paths, device="cuda", fp8_weights="fold"):
         te = build_text_encoder(sd, device)
         if te is not None:
             out["wan_video_text_encoder"] = te
+            continue
+        ie = build_image_encoder(sd, device)
+        if ie is not None:
+            out["wan_video_image_encoder"] = ie
             continue
         if sd and all(k.startswith("vace") for k in sd):
             # a VACE-module-only file (the ComfyUI workflow's WanVideoVACEModelSelect input): built

@@ -541,6 +541,7 @@ class WanVideoPipeline:
         pipe.vace2 = models.get("wan_video_vace2")
         pipe.vae = models.get("wan_video_vae")
         pipe.text_encoder = models.get("wan_video_text_encoder")
+        pipe.image_encoder = models.get("wan_video_image_encoder")
         if pipe.text_encoder is not None:
             from .t5 import WanPrompter
             tok = None
@@ -821,8 +822,9 @@ class WanVideoPipeline:
         """wan_video_new.py:416-560 for the Ditto path (T2V/VACE/video-to-video) and image-to-video (no
         audio/camera inputs).  input_image (and end_image) on a DiT with in_dim > 16 become y
         (encode_input_image) for both experts; a DiT that also takes CLIP features (has_image_input with
-        require_clip_embedding: the Wan2.1 I2V / FLF2V / Fun-InP checkpoints) needs them precomputed as
-        clip_feature= [1, 257 or 514, 1280] -- this build has no image_encoder.  With dit2 loaded the steps below switch_DiT_boundary run on dit2 / vace2 and cfg_scale
+        require_clip_embedding: the Wan2.1 I2V / FLF2V / Fun-InP checkpoints) gets them from
+        pipe.image_encoder (encode_clip_image; loaded by from_pretrained from the CLIP checkpoint) or
+        precomputed as clip_feature= [1, 257 or 514, 1280], which wins.  With dit2 loaded the steps below switch_DiT_boundary run on dit2 / vace2 and cfg_scale
         may be a (low_noise, high_noise) pair (denoise).  input_video (or its precomputed latents input_latents (1, 16, T', h, w)) with
         denoising_strength < 1 starts the loop from the video's latents re-noised to the first sigma
         of the shortened schedule (WanVideoUnit_InputVideoEmbedder, :591-614)."""
@@ -863,6 +865,10 @@ class WanVideoPipeline:
         y = None
         if input_image is not None:
             y = self.encode_input_image(input_image, end_image, num_frames, height, width, tiled, tile_size, tile_stride)
+        # WanVideoUnit_ImageEmbedderCLIP (wan_video_new.py:682-693); an explicit clip_feature= wins
+        if clip_feature is None and input_image is not None and self.image_encoder is not None and \
+                self.dit is not None and self.dit.require_clip_embedding:
+            clip_feature = self.encode_clip_image(input_image, end_image, height, width)
         tea_cache = None
         if tea_cache_l1_thresh is not None:                # WanVideoUnit_TeaCache (:936-947)
             from .teacache import TeaCache
@@ -958,9 +964,36 @@ class WanVideoPipeline:
                                               f"{d.in_dim} (Fun-Control) also needs control latents")
         for d in dits:
             if d.has_image_input and d.require_clip_embedding and clip_feature is None and \
-                    (input_image is not None or d.in_dim > 16):
+                    (input_image is not None or d.in_dim > 16) and \
+                    (self.image_encoder is None or input_image is None):
                 raise ValueError("this DiT attends to CLIP image features: pass clip_feature= ([1, 257 or 514, 1280], "
                                  "the CLIP ViT-H features of the input image); this build has no image_encoder")
+
+    def _image_frame(self, img, name, height, width):
+        """One image of __call__ as the (1, 3, 1, H, W) bf16 frame in [-1, 1] of preprocess_video: a PIL
+        image is resized to (width, height) with PIL's default resample, as the reference does; a uint8
+        (H, W, 3) tensor / array must already be height x width."""
+        from .vae import frames_to_u8, preprocess_video
+        if hasattr(img, "resize") and hasattr(img, "convert"):
+            img = img.resize((width, height))
+        elif isinstance(img, torch.Tensor) and img.dim() == 3:
+            img = img[None]
+        u8 = frames_to_u8(img if isinstance(img, torch.Tensor) else [img], self.device)
+        if tuple(u8.shape) != (1, height, width, 3):
+            raise ValueError(f"{name} must be one {height}x{width} RGB image, got {tuple(u8.shape)}")
+        return preprocess_video(u8)
+
+    def encode_clip_image(self, input_image, end_image, height, width):
+        """WanVideoUnit_ImageEmbedderCLIP (wan_video_new.py:675-693) -> clip_feature (1, 257, 1280) bf16:
+        image_encoder.encode_image of the frame encode_input_image builds; end_image's features follow
+        along dim 1 (514 rows) only when dit.has_image_pos_emb."""
+        if self.image_encoder is None:
+            raise RuntimeError("CLIP features need a loaded image_encoder (or pass clip_feature=)")
+        feat = self.image_encoder.encode_image([self._image_frame(input_image, "input_image", height, width)[:, :, 0]])
+        if end_image is not None and self.dit is not None and self.dit.has_image_pos_emb:
+            end = self.image_encoder.encode_image([self._image_frame(end_image, "end_image", height, width)[:, :, 0]])
+            feat = torch.cat([feat, end], dim=1)
+        return feat.to(self.torch_dtype)
 
     def encode_input_image(self, input_image, end_image, num_frames, height, width, tiled=True, tile_size=(30, 52),
                            tile_stride=(15, 26)):
@@ -968,22 +1001,10 @@ class WanVideoPipeline:
         mask channels (image_mask) over the 16 VAE latents of [image, zeros ... (, end_image)].  A PIL
         image is resized to (width, height) with PIL's default resample, as the reference does; a uint8
         (H, W, 3) tensor / array must already be height x width."""
-        from .vae import frames_to_u8, preprocess_video
         if self.vae is None:
             raise RuntimeError("input_image encoding requires a loaded Wan2.1 VAE")
-
-        def frame(img, name):
-            if hasattr(img, "resize") and hasattr(img, "convert"):
-                img = img.resize((width, height))
-            elif isinstance(img, torch.Tensor) and img.dim() == 3:
-                img = img[None]
-            u8 = frames_to_u8(img if isinstance(img, torch.Tensor) else [img], self.device)
-            if tuple(u8.shape) != (1, height, width, 3):
-                raise ValueError(f"{name} must be one {height}x{width} RGB image, got {tuple(u8.shape)}")
-            return preprocess_video(u8)
-
-        image = frame(input_image, "input_image")
-        end = None if end_image is None else frame(end_image, "end_image")
+        image = self._image_frame(input_image, "input_image", height, width)
+        end = None if end_image is None else self._image_frame(end_image, "end_image", height, width)
         vae_input = image_vae_input(image, end, num_frames)
         lat = self.vae.encode(vae_input.to(self.torch_dtype), self.device, tiled=tiled, tile_size=tile_size,
                               tile_stride=tile_stride)

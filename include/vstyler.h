@@ -74,7 +74,11 @@ typedef struct vs_epilogue {
     float hint_scale;
     float alpha;
     int rows_per_batch;
-    int reserved;
+    /* VS_EPI_GATE_RES only.  0: gate row b = m / rows_per_batch.  > 0: two gate rows per sample, row m
+     * reads gate row 2*b + ((m - b*rows_per_batch) >= seg_rows) (a table of 2*batches rows of stride
+     * gate_bstride; seg_rows >= rows_per_batch: every row is segment 0).  < 0: VS_E_INVALID.  Same
+     * operations and rounding points either way.  vs_residual_layernorm: VS_E_UNSUPPORTED when > 0. */
+    int seg_rows;
 } vs_epilogue;
 
 /*

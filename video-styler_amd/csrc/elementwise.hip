@@ -3,6 +3,7 @@
 // registers between the reduction and the write (one HBM read + one write per element).
 #include "common.h"
 #include "../../include/vstyler_image.h"
+#include "../../include/vstyler_seg.h"
 
 namespace {
 
@@ -64,12 +65,14 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 // quantisation (layers.py:115-151, vs_quant_fp8_rows): per-row s = max(bf16(max|h| / 448), 1) and
 // e4m3(h / (s + 1e-8)) of the bf16 values h the plain kernel would store -- bit-identical to the two
 // passes, without the bf16 write and the quantisation's read (the row's consumer is an fp8 GEMM).
-template <bool Q8, int MC = MAXCH>
+// SEG (vs_layernorm_modulate_seg): two modulation rows per sample, row r of sample b reads row
+// 2 b + ((r - b rpb) >= segr) -- the first-frame tokens of a fused-latent DiT carry timestep 0.
+template <bool Q8, int MC = MAXCH, bool SEG = false>
 __global__ __launch_bounds__(RT) void ln_modulate_kernel(
     const bf16_t* __restrict__ x, long long ldx, bf16_t* __restrict__ out, long long ldo, int dim,
     int rpb, const bf16_t* __restrict__ shift, const bf16_t* __restrict__ scale, long long mbs,
     const bf16_t* __restrict__ w, const bf16_t* __restrict__ bb, float eps, uint8_t* __restrict__ x8,
-    long long ld8, float* __restrict__ qscale) {
+    long long ld8, float* __restrict__ qscale, int segr) {
     __shared__ float red[RT / 64];
     const long long row = blockIdx.x;
     const int nch = dim >> 3;
@@ -99,7 +102,8 @@ __global__ __launch_bounds__(RT) void ln_modulate_kernel(
         }
     }
     const float rstd = rsqrtf(block_sum(q, red) / dim + eps);
-    const long long bidx = row / rpb;
+    long long bidx = row / rpb;
+    if constexpr (SEG) bidx = 2 * bidx + ((row - bidx * rpb) >= segr);
     bf16_t* orow = out + row * ldo;
 #pragma unroll
     for (int c = 0; c < MC; ++c) {
@@ -580,7 +584,7 @@ extern "C" int vs_layernorm_modulate(const void* x, long long ldx, void* out, lo
                        (hipStream_t)stream,
                        (const bf16_t*)x, ldx, (bf16_t*)out, ldo, dim, rows_per_batch,
                        (const bf16_t*)shift, (const bf16_t*)scale, mod_bstride,
-                       (const bf16_t*)weight, (const bf16_t*)bias, eps, nullptr, 0LL, nullptr);
+                       (const bf16_t*)weight, (const bf16_t*)bias, eps, nullptr, 0LL, nullptr, 0);
     VS_CHECK_LAUNCH();
     return VS_OK;
 }
@@ -601,7 +605,50 @@ extern "C" int vs_layernorm_modulate_fp8(const void* x, long long ldx, void* x8,
                        (hipStream_t)stream,
                        (const bf16_t*)x, ldx, nullptr, 0LL, dim, rows_per_batch,
                        (const bf16_t*)shift, (const bf16_t*)scale, mod_bstride,
-                       (const bf16_t*)weight, (const bf16_t*)bias, eps, (uint8_t*)x8, ld8, qscale);
+                       (const bf16_t*)weight, (const bf16_t*)bias, eps, (uint8_t*)x8, ld8, qscale, 0);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+
+// vs_layernorm_modulate / _fp8 with two modulation rows per sample (include/vstyler_seg.h): the same
+// kernels, the modulation row chosen per (sample, segment)
+extern "C" int vs_layernorm_modulate_seg(const void* x, long long ldx, void* out, long long ldo, int rows, int dim,
+                                         int rows_per_batch, int seg_rows, const void* shift, const void* scale,
+                                         long long mod_bstride, const void* weight, const void* bias, float eps,
+                                         void* stream) {
+    if (!x || !out || rows <= 0 || dim <= 0 || dim % 8 || dim > ROW_MAX) return VS_E_INVALID;
+    if (ldx < dim || ldo < dim || (ldx & 7) || (ldo & 7) || !al16(x) || !al16(out)) return VS_E_INVALID;
+    if (!shift || !scale || seg_rows < 1) return VS_E_INVALID;
+    if ((weight == nullptr) != (bias == nullptr)) return VS_E_INVALID;
+    if (!al16(shift) || !al16(scale) || (mod_bstride & 7)) return VS_E_INVALID;
+    if (weight && (!al16(weight) || !al16(bias))) return VS_E_INVALID;
+    if (rows_per_batch <= 0) rows_per_batch = rows;
+    hipLaunchKernelGGL((narrow(dim) ? ln_modulate_kernel<false, MAXCH, true> : ln_modulate_kernel<false, MCW, true>),
+                       dim3(rows), dim3(RT), 0, (hipStream_t)stream,
+                       (const bf16_t*)x, ldx, (bf16_t*)out, ldo, dim, rows_per_batch,
+                       (const bf16_t*)shift, (const bf16_t*)scale, mod_bstride,
+                       (const bf16_t*)weight, (const bf16_t*)bias, eps, nullptr, 0LL, nullptr, seg_rows);
+    VS_CHECK_LAUNCH();
+    return VS_OK;
+}
+
+extern "C" int vs_layernorm_modulate_fp8_seg(const void* x, long long ldx, void* x8, long long ld8, float* qscale,
+                                             int rows, int dim, int rows_per_batch, int seg_rows, const void* shift,
+                                             const void* scale, long long mod_bstride, const void* weight,
+                                             const void* bias, float eps, void* stream) {
+    if (!x || !x8 || !qscale || rows <= 0 || dim <= 0 || dim % 8 || dim > ROW_MAX) return VS_E_INVALID;
+    if (ldx < dim || ld8 < dim || (ldx & 7) || (ld8 & 7) || !al16(x) || (reinterpret_cast<uintptr_t>(x8) & 7))
+        return VS_E_INVALID;
+    if (!shift || !scale || seg_rows < 1) return VS_E_INVALID;
+    if ((weight == nullptr) != (bias == nullptr)) return VS_E_INVALID;
+    if (!al16(shift) || !al16(scale) || (mod_bstride & 7)) return VS_E_INVALID;
+    if (weight && (!al16(weight) || !al16(bias))) return VS_E_INVALID;
+    if (rows_per_batch <= 0) rows_per_batch = rows;
+    hipLaunchKernelGGL((narrow(dim) ? ln_modulate_kernel<true, MAXCH, true> : ln_modulate_kernel<true, MCW, true>),
+                       dim3(rows), dim3(RT), 0, (hipStream_t)stream,
+                       (const bf16_t*)x, ldx, nullptr, 0LL, dim, rows_per_batch,
+                       (const bf16_t*)shift, (const bf16_t*)scale, mod_bstride,
+                       (const bf16_t*)weight, (const bf16_t*)bias, eps, (uint8_t*)x8, ld8, qscale, seg_rows);
     VS_CHECK_LAUNCH();
     return VS_OK;
 }
@@ -615,6 +662,8 @@ extern "C" int vs_residual_layernorm(const void* y, long long ldy, void* x, long
     if (ldy < dim || ldx < dim || ldo < dim || ((ldy | ldx | ldo) & 7) || !al16(y) || !al16(x) || !al16(out))
         return VS_E_INVALID;
     if (epilogue == VS_EPI_GATE_RES) {
+        if (epi->seg_rows < 0) return VS_E_INVALID;
+        if (epi->seg_rows > 0) return VS_E_UNSUPPORTED;     // two gate rows per sample: the GEMM epilogues only
         if (!epi->gate || !al16(epi->gate) || (epi->gate_bstride & 7)) return VS_E_INVALID;
         if (epi->hint && (!al16(epi->hint) || (epi->ld_hint & 7) || epi->ld_hint < dim)) return VS_E_INVALID;
     }

@@ -44,7 +44,14 @@ struct Epi {
     int rows_per_batch;
     int mode;
     int gm;           // M-tiles per raster group of the 256x256 tile order (VS_GEMM_GM)
+    int seg_rows;     // > 0: two gate rows per sample (vs_epilogue.seg_rows), gate_row() below
 };
+
+// the gate row of output row m: its sample, or with two rows per sample 2 b + (the row's segment)
+__device__ __forceinline__ int gate_row(int m, const Epi& ep) {
+    const int b = m / ep.rows_per_batch;
+    return ep.seg_rows ? 2 * b + ((m - b * ep.rows_per_batch) >= ep.seg_rows) : b;
+}
 
 __device__ __forceinline__ int g_off(int row, int ch) { return row * 128 + 16 * (ch ^ (row & 7)); }
 
@@ -66,7 +73,6 @@ __device__ __forceinline__ void loadw(const bf16_t* p, float* v) {
 template <int W>
 __device__ __forceinline__ void epilogue_store_w(const float* a, int m, int n, bf16_t* C, long long ldc,
                                                  const Epi& ep) {
-    const int bidx = m / ep.rows_per_batch;
     float bv[W] = {};
     if (ep.bias) loadw<W>(ep.bias + n, bv);
     float y[W];
@@ -81,7 +87,7 @@ __device__ __forceinline__ void epilogue_store_w(const float* a, int m, int n, b
     } else if (ep.mode == VS_EPI_GATE_RES) {
         float rv[W], gv[W];
         loadw<W>(ep.res + (long long)m * ep.ld_res + n, rv);
-        loadw<W>(ep.gate + (long long)bidx * ep.gate_bstride + n, gv);
+        loadw<W>(ep.gate + (long long)gate_row(m, ep) * ep.gate_bstride + n, gv);
 #pragma unroll
         for (int e = 0; e < W; ++e) y[e] = rbf(rv[e] + rbf(gv[e] * y[e]));
         if (ep.hint) {
@@ -677,6 +683,12 @@ constexpr int w4_epi_min_vmem(int mode) {
     return W4_EPI_ROWS * W4_EPI_CBLK * ((mode == VS_EPI_GATE_RES || mode == VS_EPI_RES) ? 2 : 1);
 }
 
+// The gate rows of a wave's 128-row window: the two cached rows are those of the window's first and last
+// row, and a row takes the second from m_hi on, the first row that does not read the first's (one
+// compare per row step; the row's own m / rows_per_batch it replaces was a division per row step).
+// With two gate rows per sample (Epi::seg_rows > 0, gate_row) that is right while the window holds at
+// most two gate rows, i.e. no non-empty segment is shorter than 128 rows: the host's condition for
+// this kernel (seg_short).
 template <int MODE, bool HINT, bool SCALED, class AccT>
 __device__ __forceinline__ void tile_epilogue_w4(const AccT& acc, int m_w, int n_w, int lane, bf16_t* C, long long ldc,
                                                  int M, int N, const Epi& ep, const float* __restrict__ scale_a) {
@@ -705,9 +717,20 @@ __device__ __forceinline__ void tile_epilogue_w4(const AccT& acc, int m_w, int n
         unpack8(ep.bias ? ld16(ep.bias + min(nl + 32 * p, N - 8)) : u32x4_t{0, 0, 0, 0}, bvf[p]);
     u32x4_t gw0[4], gw1[4];
     int b_lo = 0;
+    unsigned m_hi = 0;
     if constexpr (MODE == VS_EPI_GATE_RES) {
         b_lo = min(m_w, M - 1) / ep.rows_per_batch;
-        const int b_hi = min(m_w + 127, M - 1) / ep.rows_per_batch;
+        int b_hi = min(m_w + 127, M - 1) / ep.rows_per_batch;
+        const int rpb = ep.rows_per_batch;
+        m_hi = (unsigned)b_lo * (unsigned)rpb + (unsigned)rpb;
+        if (ep.seg_rows) {
+            const int first = min(m_w, M - 1), last = min(m_w + 127, M - 1);
+            const bool s_lo = first - b_lo * rpb >= ep.seg_rows, s_hi = last - b_hi * rpb >= ep.seg_rows;
+            // the first row past `first`'s segment (an empty segment 1 ends segment 0 at the sample's end)
+            if (!s_lo && ep.seg_rows < rpb) m_hi = (unsigned)b_lo * (unsigned)rpb + (unsigned)ep.seg_rows;
+            b_lo = 2 * b_lo + s_lo;
+            b_hi = 2 * b_hi + s_hi;
+        }
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             const int n = min(nl + 32 * p, N - 8);
@@ -774,7 +797,7 @@ __device__ __forceinline__ void tile_epilogue_w4(const AccT& acc, int m_w, int n
                                                 : pk_store(silu_f(v.x), silu_f(v.y));
                 }
             } else if constexpr (MODE == VS_EPI_GATE_RES) {
-                const bool hi = m / ep.rows_per_batch != b_lo;
+                const bool hi = (unsigned)m >= m_hi;
                 const u32x4_t gsel = hi ? gw1[p] : gw0[p];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -2249,6 +2272,10 @@ static int fill_epi(Epi& ep, int epilogue, const vs_epilogue* epi, int m, int n)
         ep.hint_scale = epi->hint_scale;
         ep.alpha = epi->alpha;
         if (epi->rows_per_batch > 0) ep.rows_per_batch = epi->rows_per_batch;
+        if (epilogue == VS_EPI_GATE_RES) {
+            if (epi->seg_rows < 0) return VS_E_INVALID;
+            ep.seg_rows = epi->seg_rows;
+        }
     }
     if ((epilogue == VS_EPI_GATE_RES || epilogue == VS_EPI_RES) && (!ep.res || ep.ld_res < n)) return VS_E_INVALID;
     if (epilogue == VS_EPI_GATE_RES && !ep.gate) return VS_E_INVALID;
@@ -2323,7 +2350,16 @@ static KF4 fp8_4w(int i) {
                       gemm_fp8_tn_4w<false, VS_EPI_BIAS, false>};
     return t[i];
 }
+constexpr int N4W_BF16 = 6, N4W_FP8 = 7;
 static int mode_4w(const Epi& ep) { return (ep.mode == VS_EPI_GATE_RES && ep.hint) ? 5 : ep.mode; }
+// two gate rows per sample with a non-empty segment shorter than 128 rows: a wave's 128-row window of
+// the 4-wave epilogue (two cached gate rows) can then hold three, so such launches take a kernel with
+// the per-row epilogue (epilogue_store_w)
+static bool seg_short(const Epi& ep) {
+    if (ep.mode != VS_EPI_GATE_RES || !ep.seg_rows) return false;
+    const int s0 = ep.seg_rows < ep.rows_per_batch ? ep.seg_rows : ep.rows_per_batch, s1 = ep.rows_per_batch - s0;
+    return s0 < 128 || (s1 > 0 && s1 < 128);
+}
 
 // every instantiation's dynamic-LDS limit, set once, before the first GEMM launch
 static void set_lds_limits() {
@@ -2343,8 +2379,8 @@ static void set_lds_limits() {
             set(f, LDS8 + 1024);
         for (const void* f : {(const void*)gemm_fp8_tn_8p<true, false, true>, (const void*)gemm_fp8_tn_8p<true, true, true>})
             set(f, LDS8 + 2048);
-        for (int i = 0; i < 6; ++i) set((const void*)bf16_4w(i), W4_LDS + 16);
-        for (int i = 0; i < 7; ++i) set((const void*)fp8_4w(i), F4_LDS + 16);
+        for (int i = 0; i < N4W_BF16; ++i) set((const void*)bf16_4w(i), W4_LDS + 16);
+        for (int i = 0; i < N4W_FP8; ++i) set((const void*)fp8_4w(i), F4_LDS + 16);
         return true;
     }();
     (void)done;
@@ -2368,10 +2404,12 @@ extern "C" int vs_gemm(const void* a, long long lda, const void* w, long long ld
     // (VS_OPT_GEMM_TILE forces one).  r5: the 1.3B model's K = 1536 block GEMMs run 1314-1497 TF/s on
     // the 4-wave kernel against 606-861 on the 128x128 one (profiles/r5/gemm_ab_1p3b_s3.log), and the
     // 160-tile context k|v GEMM (M = 1024, K = 4096) is one 4-wave round instead of 218 us of 128x128
+    // (every launch of a 4-wave kernel must hold !seg_short(ep): tile_epilogue_w4's two cached gate rows)
+    const bool use4 = use_4w() && !seg_short(ep);
     const int force = vs_opt(VS_OPT_GEMM_TILE);
     const long long tiles256 = (long long)((m + BT - 1) / BT) * ((n + BT - 1) / BT);
     const bool big = force ? force == 256
-                           : (tiles256 >= 240 && k >= 4096) || (tiles256 >= 128 && k >= 1024 && k2 == 0 && use_4w());
+                           : (tiles256 >= 240 && k >= 4096) || (tiles256 >= 128 && k >= 1024 && k2 == 0 && use4);
     if (!big) {
         const int ntm = (m + BM - 1) / BM, ntn = (n + BN - 1) / BN;
         const long long nwg = (long long)ntm * ntn;
@@ -2386,7 +2424,7 @@ extern "C" int vs_gemm(const void* a, long long lda, const void* w, long long ld
     // LoRA second phase
     const int tm = (m + BT - 1) / BT, tn = (n + BT - 1) / BT;
     const bool wide = epi_wide(ep, n, c, ldc);
-    const bool w4 = k2 == 0 && wide && use_4w();
+    const bool w4 = k2 == 0 && wide && use4;
     float* part = nullptr;
     KSplit sp = k2 ? KSplit{tm * tn, 0, 1, 0} : split_tail(tm * tn, k, 64, stream, part);
     if (w4 && vs_opt(VS_OPT_QUEUE) && vs_opt(VS_OPT_PIECE_QUEUE) == 2 && vs_opt(VS_OPT_GEMM_SPLIT)) {
@@ -2400,7 +2438,7 @@ extern "C" int vs_gemm(const void* a, long long lda, const void* w, long long ld
             }
         }
     }
-    if (w4) {
+    if (w4) {       // (w4 implies !seg_short(ep), which tile_epilogue_w4's gate-row cache relies on)
         // raster groups of 2 M-tiles for the deep-K FFN-down (K 13 824: 5.47-5.48 vs 5.54-5.57 ms at
         // 59 280 rows), 4 elsewhere (q|k|v / FFN-up 1-1.5 % slower at 2, 5-15 % at 8-16;
         // profiles/r6/gemm_gm_s10.log).  The split combine below reads the same ep.gm
@@ -2435,7 +2473,9 @@ static int gemm_fp8_impl(const void* a8, long long lda, const float* scale_a, co
     const bool wide = epi_wide(ep, n, c, ldc);
     float* part = nullptr;
     const KSplit sp = split_tail(tm * tn, k, 128, stream, part);
-    if (!scale_w && use_4w()) {            // the 4-wave kernel unless VS_OPT_GEMM_KERNEL 8
+    if (!scale_w && use_4w() && !seg_short(ep)) {   // the 4-wave kernel unless VS_OPT_GEMM_KERNEL 8 (or a short segment)
+        // (!seg_short(ep) is a precondition of this launch, not a preference: tile_epilogue_w4 caches two
+        // gate rows per 128-row window and a shorter segment can put three in one)
         // persistent blocks fed by the XCD tile queues, as the bf16 kernel (w4_sched)
         const W4Sched sc = w4_sched(sp.nmain, k / 128, stream);
         hipLaunchKernelGGL(fp8_4w(wide ? mode_4w(ep) : 6), dim3(w4_grid(sc, sp)), dim3(256), F4_LDS + 16, stream,

@@ -1,5 +1,5 @@
-"""ctypes binding of libvstyler.so (the C ABI declared in include/vstyler.h, vstyler_image.h and
-vstyler_clip.h).
+"""ctypes binding of libvstyler.so (the C ABI declared in include/vstyler.h, vstyler_image.h,
+vstyler_clip.h and vstyler_seg.h).
 
 The product path has no CPU fallback: if the library is missing every op raises.
 """
@@ -29,7 +29,7 @@ class VsEpilogue(ctypes.Structure):
         ("hint_scale", ctypes.c_float),
         ("alpha", ctypes.c_float),
         ("rows_per_batch", ctypes.c_int),
-        ("reserved", ctypes.c_int),
+        ("seg_rows", ctypes.c_int),
     ]
 
 
@@ -129,6 +129,11 @@ SIGNATURES_IMAGE = {
 SIGNATURES_CLIP = {
     "vs_clip_preprocess": [_P, _LL, _LL, _LL, _P, _LL, _I, _I, _I, _I, _P],
 }
+# two modulation rows per sample (include/vstyler_seg.h): a fourth table
+SIGNATURES_SEG = {
+    "vs_layernorm_modulate_seg": [_P, _LL, _P, _LL, _I, _I, _I, _I, _P, _P, _LL, _P, _P, _F, _P],
+    "vs_layernorm_modulate_fp8_seg": [_P, _LL, _P, _LL, _P, _I, _I, _I, _I, _P, _P, _LL, _P, _P, _F, _P],
+}
 _RESTYPES = {"vs_strerror": ctypes.c_char_p, "vs_split_workspace_bytes": ctypes.c_longlong,
              "vs_sp_last_error": ctypes.c_char_p}
 
@@ -144,7 +149,8 @@ def load():
                 f"libvstyler.so not found at {LIB_PATH}: build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or make -C video-styler_amd/csrc)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in list(SIGNATURES.items()) + list(SIGNATURES_IMAGE.items()) + list(SIGNATURES_CLIP.items()):
+        for name, argtypes in (list(SIGNATURES.items()) + list(SIGNATURES_IMAGE.items()) +
+                               list(SIGNATURES_CLIP.items()) + list(SIGNATURES_SEG.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, ctypes.c_int)

@@ -117,8 +117,9 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _epilogue(bias, residual, gate, gate_bstride, hint, hint_scale, alpha, rows_per_batch):
+def _epilogue(bias, residual, gate, gate_bstride, hint, hint_scale, alpha, rows_per_batch, seg_rows=0):
     ep = VsEpilogue()
+    ep.seg_rows = int(seg_rows)
     ep.bias = _ptr(bias)
     ep.hint_scale = float(hint_scale)
     ep.alpha = float(alpha)
@@ -135,14 +136,16 @@ def _epilogue(bias, residual, gate, gate_bstride, hint, hint_scale, alpha, rows_
 
 
 def gemm(a, w, out, epilogue=VS_EPI_BIAS, bias=None, residual=None, gate=None, gate_bstride=0,
-         hint=None, hint_scale=1.0, alpha=1.0, rows_per_batch=0, a2=None, w2=None):
-    """out[M,N] = epilogue(a[M,K] @ w[N,K]^T (+ a2 @ w2^T)) (see include/vstyler.h vs_gemm)."""
+         hint=None, hint_scale=1.0, alpha=1.0, rows_per_batch=0, a2=None, w2=None, seg_rows=0):
+    """out[M,N] = epilogue(a[M,K] @ w[N,K]^T (+ a2 @ w2^T)) (see include/vstyler.h vs_gemm).
+    seg_rows > 0 (VS_EPI_GATE_RES): gate holds two rows per sample, rows past the first seg_rows of a
+    sample read the second (vs_epilogue.seg_rows)."""
     M, K, lda = _rows(a, "a")
     N, Kw, ldw = _rows(w, "w")
     Mo, No, ldc = _rows(out, "out")
     if Kw != K or Mo != M or No != N:
         raise ValueError(f"gemm shape mismatch a={tuple(a.shape)} w={tuple(w.shape)} out={tuple(out.shape)}")
-    ep = _epilogue(bias, residual, gate, gate_bstride, hint, hint_scale, alpha, rows_per_batch)
+    ep = _epilogue(bias, residual, gate, gate_bstride, hint, hint_scale, alpha, rows_per_batch, seg_rows)
     k2, lda2, ldw2 = 0, 0, 0
     if a2 is not None:
         _, k2, lda2 = _rows(a2, "a2")
@@ -200,11 +203,11 @@ def _weight_scale(scale_w, w8):
 
 
 def gemm_fp8(a8, scale_a, w8, out, epilogue=VS_EPI_BIAS, bias=None, residual=None, gate=None, gate_bstride=0,
-             hint=None, hint_scale=1.0, alpha=1.0, rows_per_batch=0, a2=None, w2=None, scale_w=None):
+             hint=None, hint_scale=1.0, alpha=1.0, rows_per_batch=0, a2=None, w2=None, scale_w=None, seg_rows=0):
     """out = epilogue(scale_a[m] * (a8 @ w8^T) (+ a2 @ w2^T)) with e4m3 operands a8 / w8 and the bf16
     un-merged LoRA phase a2 [M, k2] / w2 [N, k2] (see vs_gemm_fp8, vs_gemm_fp8_lora).  scale_w (fp32
     [N]): the per-output-channel weight scale, out = epilogue(((a8 @ w8^T) * scale_w[n]) * scale_a[m]
-    (+ a2 @ w2^T)) through vs_gemm_fp8_ws; None runs the entry points above."""
+    (+ a2 @ w2^T)) through vs_gemm_fp8_ws; None runs the entry points above.  seg_rows: as gemm()."""
     if scale_w is not None:
         _weight_scale(scale_w, w8)
     if a2 is not None or w2 is not None:
@@ -214,7 +217,7 @@ def gemm_fp8(a8, scale_a, w8, out, epilogue=VS_EPI_BIAS, bias=None, residual=Non
     Mo, No, ldc = _rows(out, "out")
     if Kw != K or Mo != M or No != N or scale_a.dtype != torch.float32:
         raise ValueError(f"gemm_fp8 shape mismatch a8={tuple(a8.shape)} w8={tuple(w8.shape)} out={tuple(out.shape)}")
-    ep = _epilogue(bias, residual, gate, gate_bstride, hint, hint_scale, alpha, rows_per_batch)
+    ep = _epilogue(bias, residual, gate, gate_bstride, hint, hint_scale, alpha, rows_per_batch, seg_rows)
     k2 = a2.shape[1] if a2 is not None else 0
     lda2 = ldw2 = 0
     if k2 > 0:                                      # whole-tile grid, no workspace
@@ -317,6 +320,36 @@ def layernorm_modulate_fp8(x, x8, qscale, eps=1e-6, shift=None, scale=None, mod_
                                                      M, D, int(rows_per_batch), _ptr(shift), _ptr(scale),
                                                      int(mod_bstride), _ptr(weight), _ptr(bias), float(eps),
                                                      _stream(x)))
+    return x8, qscale
+
+
+def layernorm_modulate_seg(x, out, seg_rows, eps=1e-6, shift=None, scale=None, mod_bstride=0, rows_per_batch=0,
+                           weight=None, bias=None):
+    """layernorm_modulate with two modulation rows per sample (vs_layernorm_modulate_seg): row r of
+    sample b reads row 2 b + (r >= seg_rows) of shift / scale."""
+    M, D, ldx = _rows(x, "x")
+    Mo, Do, ldo = _rows(out, "out")
+    if Mo != M or Do != D:
+        raise ValueError("layernorm_modulate_seg: shape mismatch")
+    _lib.check(_lib.load().vs_layernorm_modulate_seg(x.data_ptr(), ldx, out.data_ptr(), ldo, M, D,
+                                                     int(rows_per_batch), int(seg_rows), _ptr(shift), _ptr(scale),
+                                                     int(mod_bstride), _ptr(weight), _ptr(bias), float(eps),
+                                                     _stream(x)))
+    return out
+
+
+def layernorm_modulate_fp8_seg(x, x8, qscale, seg_rows, eps=1e-6, shift=None, scale=None, mod_bstride=0,
+                               rows_per_batch=0, weight=None, bias=None):
+    """layernorm_modulate_fp8 with two modulation rows per sample (vs_layernorm_modulate_fp8_seg)."""
+    M, D, ldx = _rows(x, "x")
+    if x8.dtype != torch.uint8 or x8.dim() != 2 or x8.shape[0] != M or x8.shape[1] < D or x8.stride(1) != 1:
+        raise ValueError("layernorm_modulate_fp8_seg: x8 must be uint8 [M, >=D] with unit column stride")
+    if qscale.dtype != torch.float32 or qscale.numel() < M or not qscale.is_contiguous():
+        raise ValueError("layernorm_modulate_fp8_seg: qscale must be contiguous float32 [M]")
+    _lib.check(_lib.load().vs_layernorm_modulate_fp8_seg(x.data_ptr(), ldx, x8.data_ptr(), x8.stride(0),
+                                                         qscale.data_ptr(), M, D, int(rows_per_batch), int(seg_rows),
+                                                         _ptr(shift), _ptr(scale), int(mod_bstride), _ptr(weight),
+                                                         _ptr(bias), float(eps), _stream(x)))
     return x8, qscale
 
 

@@ -30,6 +30,15 @@ WAN_I2V_DIT_CONFIGS = {
     "349723183fc063b2bfc10bb2835cf677": dict(dim=1536, ffn_dim=8960, num_heads=12, num_layers=30, in_dim=48,
                                              has_image_input=True),                          # Fun-1.3B-Control
 }
+# Wan2.2-TI2V-5B (wan_video_dit.py:678-696): 48 latent channels in and out, no y and no CLIP branch; in
+# its image-to-video mode the clean first-frame latents sit in latent frame 0, whose tokens run at
+# timestep 0 (seperated_timestep / fuse_vae_embedding_in_latents).  A third table, looked up last.
+WAN_TI2V_DIT_CONFIGS = {
+    "1f5ab7703c6fc803fdded85ff040c316": dict(dim=3072, ffn_dim=14336, num_heads=24, num_layers=30, in_dim=48,
+                                             out_dim=48, has_image_input=False, seperated_timestep=True,
+                                             require_clip_embedding=False, require_vae_embedding=False,
+                                             fuse_vae_embedding_in_latents=True),
+}
 WAN_COMMON = dict(in_dim=16, out_dim=16, text_dim=4096, freq_dim=256, eps=1e-6, patch_size=(1, 2, 2))
 VACE_14B_HASH = "3b2726384e4f64837bdf216eea3f310d"
 VACE_14B = dict(vace_layers=(0, 5, 10, 15, 20, 25, 30, 35), vace_in_dim=96, patch_size=(1, 2, 2),
@@ -204,8 +213,8 @@ def vace_config_from_shapes(sd, num_layers):
 def build_dit(state_dict, device):
     sd = {k: v for k, v in state_dict.items() if not k.startswith("vace")}
     h = hash_state_dict_keys(sd)
-    if h in WAN_DIT_CONFIGS or h in WAN_I2V_DIT_CONFIGS:
-        cfg = dict(WAN_COMMON, **(WAN_DIT_CONFIGS.get(h) or WAN_I2V_DIT_CONFIGS[h]))
+    if h in WAN_DIT_CONFIGS or h in WAN_I2V_DIT_CONFIGS or h in WAN_TI2V_DIT_CONFIGS:
+        cfg = dict(WAN_COMMON, **(WAN_DIT_CONFIGS.get(h) or WAN_I2V_DIT_CONFIGS.get(h) or WAN_TI2V_DIT_CONFIGS[h]))
     else:
         cfg = dit_config_from_shapes(sd)
         if cfg is None:

@@ -55,11 +55,17 @@ def ln_into(x, h, ws, target, eps, **ln):
     """LayerNorm(+modulate) of x for `target`'s projection: into the bf16 buffer h, or -- when target
     runs fp8_linear -- straight into its quantised activation (vs_layernorm_modulate_fp8: the bf16 row
     is never stored and not re-read; bit-identical)."""
+    seg = ln.pop("seg_rows", 0)     # two modulation rows per sample (RunCtx.seg_rows): the _seg entries
     if target is not None and _fp8_consumer(target):
         M, D = x.shape
-        return Q8(*K.layernorm_modulate_fp8(x, ws.get("fp8_x", (M, D), torch.uint8),
-                                            ws.get("fp8_scale", (M,), torch.float32), eps, **ln))
-    K.layernorm_modulate(x, h, eps, **ln)
+        x8, qs = ws.get("fp8_x", (M, D), torch.uint8), ws.get("fp8_scale", (M,), torch.float32)
+        if seg:
+            return Q8(*K.layernorm_modulate_fp8_seg(x, x8, qs, seg, eps, **ln))
+        return Q8(*K.layernorm_modulate_fp8(x, x8, qs, eps, **ln))
+    if seg:
+        K.layernorm_modulate_seg(x, h, seg, eps, **ln)
+    else:
+        K.layernorm_modulate(x, h, eps, **ln)
     return h
 
 
@@ -439,6 +445,14 @@ class RunCtx:
         # image conditioning: the embedded CLIP rows every block's image cross-attention reads,
         # [img_batch * IMG_TOKENS, D] (img_batch 1: one key set shared by every CFG sample), or None
         self.img, self.img_batch = None, 0
+        # two modulation rows per sample (a fused-first-frame DiT, model_fn_wan_video): the first
+        # seg_rows token rows of every sample read modulation row 2 b, the rest 2 b + 1; 0: one row
+        self.seg_rows = 0
+
+    @property
+    def seg(self):
+        """The seg_rows= keyword of the modulated LayerNorms and the gated GEMMs (none when unsegmented)."""
+        return {"seg_rows": self.seg_rows} if self.seg_rows else {}
 
 
 class DiTBlock(nn.Module):
@@ -454,7 +468,8 @@ class DiTBlock(nn.Module):
         self.modulation = _param(1, 6, dim, device=device)
 
     def forward(self, x, t_mod, rc, hint=None, hint_scale=1.0, only_batch=None, shared_prefix=False):
-        """x: [B*S, D] updated in place.  t_mod: [B, 6, D].  hint: [B*S, D] added after the block.
+        """x: [B*S, D] updated in place.  t_mod: [B, 6, D] ([2 B, 6, D] with rc.seg_rows: sample b's two
+        segments' rows at 2 b and 2 b + 1).  hint: [B*S, D] added after the block.
         only_batch: run the block for that CFG sample only (skip-layer guidance leaves the others'
         rows untouched).  Every GEMM fuses its epilogue (residual, gate, hint); each LayerNorm is a pass
         of its own.
@@ -478,7 +493,8 @@ class DiTBlock(nn.Module):
         B, S, D, ws = rc.batch, rc.seq, self.dim, rc.ws
         # one buffer for every block: mod_add and every kernel that reads mod (the LayerNorms, the
         # gated GEMM epilogues) are enqueued on the current stream; side streams carry collectives only
-        mod = ws.get("mod", (B, 6, D))
+        nm = 2 if rc.seg_rows else 1
+        mod = ws.get("mod", (nm * B, 6, D))
         K.mod_add(self.modulation.view(6, D), t_mod, mod, 6 * D, D)   # :218-219
         sp = rc.sp
         shared = shared_prefix and B > 1 and only_batch is None and bool(host_option("cfg_prefix"))
@@ -512,7 +528,8 @@ class DiTBlock(nn.Module):
     def _part(self, x, mod, rc, b0, nb, hint, tag):
         S, D, L, ws = rc.seq, self.dim, rc.ctx_len, rc.ws
         r0, M = b0 * S, nb * S
-        p = dict(nb=nb, M=M, x=x[r0:r0 + M], mod=mod[b0:b0 + nb], ctx=rc.ctx[b0 * L:(b0 + nb) * L],
+        nm = 2 if rc.seg_rows else 1
+        p = dict(nb=nb, M=M, x=x[r0:r0 + M], mod=mod[nm * b0:nm * (b0 + nb)], ctx=rc.ctx[b0 * L:(b0 + nb) * L],
                  hint=None if hint is None else hint[r0:r0 + M], tag=tag)
         if rc.img is not None:          # this part's image rows: the shared set, or its samples' own
             p["img"] = rc.img if rc.img_batch == 1 else rc.img[b0 * IMG_TOKENS:(b0 + nb) * IMG_TOKENS]
@@ -526,7 +543,7 @@ class DiTBlock(nn.Module):
         mod, h, q, k, v = p["mod"], p["h"], p["q"], p["k"], p["v"]
         sa = self.self_attn
         h = ln_into(p["x"], h, ws, sa, eps, shift=mod[:, 0], scale=mod[:, 1], mod_bstride=6 * D,
-                    rows_per_batch=S)
+                    rows_per_batch=S, **rc.seg)
         qkv = fused_linear(sa, h, ws, "qkv" + p["tag"])
         if qkv is not None:            # one GEMM; q/k/v are column slices of [M, 3D]
             q, k, v = p["q"], p["k"], p["v"] = qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:]
@@ -557,7 +574,7 @@ class DiTBlock(nn.Module):
         if rc.sp is not None:
             rc.sp.finish(p["xchg"], o)
         linear(self.self_attn.o, o, x, ws, epilogue=K.VS_EPI_GATE_RES, residual=x, gate=mod[:, 2],
-               gate_bstride=6 * D, rows_per_batch=S)
+               gate_bstride=6 * D, rows_per_batch=S, **rc.seg)
         # --- cross-attention (wan_video_dit.py:227, :171-186)
         p["h3"] = ln_into(x, h, ws, self.cross_attn.q if direct else None, eps, weight=self.norm3.weight,
                           bias=self.norm3.bias)
@@ -588,11 +605,12 @@ class DiTBlock(nn.Module):
         linear(ca.o, o, x, ws, epilogue=K.VS_EPI_RES, residual=x)
         # --- FFN (wan_video_dit.py:228-229) + VACE hint (wan_video_new.py:1450)
         h = ln_into(x, h, ws, self.ffn[0], eps, shift=mod[:, 3], scale=mod[:, 4], mod_bstride=6 * D,
-                    rows_per_batch=S)
+                    rows_per_batch=S, **rc.seg)
         f = ws.get("f" + p["tag"], (M, self.ffn_dim))
         linear(self.ffn[0], h, f, ws, epilogue=K.VS_EPI_GELU)
         linear(self.ffn[2], f, x, ws, epilogue=K.VS_EPI_GATE_RES, residual=x,
-               gate=mod[:, 5], gate_bstride=6 * D, rows_per_batch=S, hint=p["hint"], hint_scale=hint_scale)
+               gate=mod[:, 5], gate_bstride=6 * D, rows_per_batch=S, hint=p["hint"], hint_scale=hint_scale,
+               **rc.seg)
 
 
     def _image_attn(self, p, rc, q, o):
@@ -634,10 +652,11 @@ class Head(nn.Module):
     def forward(self, x, t, rc):
         B, S, D, ws = rc.batch, rc.seq, self.dim, rc.ws
         h = ws.get("h", (B * S, D))
-        hm = ws.get("head_mod", (B, 2, D))
-        K.mod_add(self.modulation.view(2, D), t, hm, D, 0)      # :267, per-batch t row
-        K.layernorm_modulate(x, h, self.eps, shift=hm[:, 0], scale=hm[:, 1], mod_bstride=2 * D,
-                             rows_per_batch=S)
+        # :267, a t row per sample; with rc.seg_rows (:263-265) t is [2 B, D]: a row per (sample, segment)
+        hm = ws.get("head_mod", ((2 if rc.seg_rows else 1) * B, 2, D))
+        K.mod_add(self.modulation.view(2, D), t, hm, D, 0)
+        ln_into(x, h, ws, None, self.eps, shift=hm[:, 0], scale=hm[:, 1], mod_bstride=2 * D, rows_per_batch=S,
+                **rc.seg)
         out = ws.get("head_out", (B * S, self.head.out_features))
         K.gemm(h, self.head.weight, out, bias=self.head.bias)
         return out
@@ -686,7 +705,8 @@ IMG_EMB_EPS = 1e-5    # nn.LayerNorm's default eps, which MLP.proj's two LayerNo
 class WanModel(nn.Module):
     """wan_video_dit.py:272-337: the T2V / VACE layout (in_dim 16) and the image-conditioned ones --
     in_dim > 16 (the VAE-embedded image `y` concatenated behind the latents: I2V, FLF2V, Fun-InP,
-    Wan2.2-I2V-A14B) with or without the CLIP image branch (has_image_input: img_emb + the blocks'
+    Wan2.2-I2V-A14B; or the 48 latent channels of Wan2.2-TI2V-5B, which takes no `y`:
+    fuse_vae_embedding_in_latents / seperated_timestep) with or without the CLIP image branch (has_image_input: img_emb + the blocks'
     k_img / v_img / norm_k_img; has_image_pos_emb: img_emb.emb_pos over 514 tokens)."""
 
     def __init__(self, dim, in_dim, ffn_dim, out_dim, text_dim, freq_dim, eps, patch_size, num_heads,
@@ -694,12 +714,14 @@ class WanModel(nn.Module):
                  add_control_adapter=False, seperated_timestep=False, require_vae_embedding=True,
                  require_clip_embedding=True, fuse_vae_embedding_in_latents=False, device=None, **kwargs):
         super().__init__()
-        for name, on in (("has_ref_conv", has_ref_conv), ("add_control_adapter", add_control_adapter),
-                         ("seperated_timestep", seperated_timestep),
-                         ("fuse_vae_embedding_in_latents", fuse_vae_embedding_in_latents)):
+        for name, on in (("has_ref_conv", has_ref_conv), ("add_control_adapter", add_control_adapter)):
             if on:
-                raise NotImplementedError(f"WanModel({name}=True) (Fun-Control reference conv, camera control, "
-                                          f"TI2V-5B) is not in this build")
+                raise NotImplementedError(f"WanModel({name}=True) (Fun-Control reference conv, camera control) "
+                                          f"is not in this build")
+        if bool(seperated_timestep) != bool(fuse_vae_embedding_in_latents):
+            # Wan2.2-TI2V-5B, the one layout with either flag, sets both; each alone is another model
+            raise NotImplementedError("WanModel: seperated_timestep and fuse_vae_embedding_in_latents go together "
+                                      "(Wan2.2-TI2V-5B); one without the other is not in this build")
         if dim // num_heads != 128:
             raise NotImplementedError("head_dim must be 128 (all Wan2.1 models)")
         if in_dim < 16:
@@ -711,10 +733,12 @@ class WanModel(nn.Module):
         self.patch_size = tuple(patch_size)
         self.has_image_input = bool(has_image_input)
         self.has_image_pos_emb = bool(has_image_pos_emb)
-        self.seperated_timestep = False
+        # Wan2.2-TI2V-5B: the first latent frame holds the clean image latents and its tokens run at
+        # timestep 0 (model_fn_wan_video(fuse_vae_embedding_in_latents=True))
+        self.seperated_timestep = bool(seperated_timestep)
         self.require_vae_embedding = bool(require_vae_embedding)
         self.require_clip_embedding = bool(require_clip_embedding)
-        self.fuse_vae_embedding_in_latents = False
+        self.fuse_vae_embedding_in_latents = bool(fuse_vae_embedding_in_latents)
         self.patch_embedding = PatchEmbed(in_dim, dim, device)
         self.text_embedding = Sequential3(Linear(text_dim, dim, device=device), Linear(dim, dim, device=device))
         self.time_embedding = Sequential3(Linear(freq_dim, dim, device=device), Linear(dim, dim, device=device))

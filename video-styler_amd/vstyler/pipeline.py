@@ -101,8 +101,17 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
                        vace_context=None, vace_scale=1.0, use_unified_sequence_parallel: bool = False,
                        sp_group=None, slg_blocks=(), tea_cache=None, cfg_sample=0, sliding_window_size=None,
                        sliding_window_stride=None, vace_context_windows=None, y=None, clip_feature=None,
-                       y_windows=None, **kwargs):
-    """One DiT(+VACE) forward (wan_video_new.py:1338-1468) -> [B,16,T,H,W] bf16 velocity.
+                       y_windows=None, fuse_vae_embedding_in_latents=False, **kwargs):
+    """One DiT(+VACE) forward (wan_video_new.py:1338-1468) -> [B,dit.out_dim,T,H,W] bf16 velocity.
+
+    fuse_vae_embedding_in_latents (with dit.seperated_timestep: Wan2.2-TI2V-5B's image-to-video mode,
+    :1339-1349): latent frame 0 holds the clean first-frame latents, so its n0 = (H/2)(W/2) tokens are
+    modulated with timestep 0 and every other token with `timestep`.  The reference builds a per-token
+    [1, S, 6, dim] modulation; it has two distinct rows, so here the time embedding runs on (0,
+    bf16(timestep)) and every modulated LayerNorm and gated GEMM picks row (token >= n0) of its sample's
+    two (RunCtx.seg_rows, include/vstyler_seg.h).  One timestep for the whole batch, as the reference.
+    Not on this path (NotImplementedError): Ulysses / CFG parallelism, more than one sliding window,
+    tea_cache, a VACE module.
 
     slg_blocks: skip-layer guidance (config 5, ComfyUI WanVideoSLG): the listed main blocks are
     skipped for CFG sample 1 (the unconditional pass), run for sample 0 only.  cfg_sample: which
@@ -132,7 +141,19 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     for name in _UNSUPPORTED:
         if kwargs.get(name) is not None:
             raise NotImplementedError(f"model_fn_wan_video: '{name}' is outside the Ditto hot path")
+    seg = bool(fuse_vae_embedding_in_latents) and bool(dit.seperated_timestep)
     win = check_window_args(sliding_window_size, sliding_window_stride)
+    if seg:
+        what = ("Ulysses / CFG parallelism" if use_unified_sequence_parallel else
+                "a temporal sliding window of more than one window"
+                if win is not None and len(plan_windows(latents.shape[2], *win).windows) > 1 else
+                "tea_cache" if tea_cache is not None else
+                "a VACE module" if vace is not None and vace_context is not None else None)
+        if what is not None:
+            raise NotImplementedError(f"model_fn_wan_video: fuse_vae_embedding_in_latents (the first-frame "
+                                      f"segment of a seperated_timestep DiT) with {what}")
+        if timestep.numel() != 1:
+            raise ValueError("model_fn_wan_video: fuse_vae_embedding_in_latents takes one timestep for the batch")
     if win is not None and len(plan_windows(latents.shape[2], *win).windows) > 1:
         if tea_cache is not None:
             # the reference hands one TeaCache state to every window (:1304), which compares and reuses
@@ -154,7 +175,7 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     if y is not None and 16 + y.shape[1] != dit.in_dim:
         raise ValueError(f"model_fn_wan_video: y has {y.shape[1]} channels, the DiT's patch embedding takes "
                          f"16 + {dit.in_dim - 16}")
-    if y is None and dit.in_dim > 16:
+    if y is None and dit.in_dim > 16 and not dit.fuse_vae_embedding_in_latents:
         raise ValueError(f"model_fn_wan_video: the DiT's patch embedding takes {dit.in_dim} channels: pass y= "
                          f"({dit.in_dim - 16} image-conditioning channels)")
     if use_unified_sequence_parallel:
@@ -200,6 +221,8 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     if timestep.shape[0] != B:
         timestep = timestep.expand(B).contiguous()
 
+    if seg:     # (0, bf16(t)) per sample: t [2 B, D], t_mod [2 B, 6, D], rows 2 b / 2 b + 1 = b's two segments
+        timestep = torch.stack([torch.zeros_like(timestep), timestep], dim=1).reshape(-1)
     t, t_mod = dit.time_embed(timestep, ws)
     ctx = dit.text_embed(context.to(BF16), ws)
     if y is None:
@@ -236,6 +259,8 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     rc = RunCtx(B, S, grid, dit.rope(device), ctx, L, ws)
     if img is not None:
         rc.img, rc.img_batch = img, clip_feature.shape[0]
+    if seg:
+        rc.seg_rows = grid[1] * grid[2]     # the tokens of latent frame 0 (T == 1: every row)
 
     vace_x = None
     if vace_context is not None and vace is not None:
@@ -589,8 +614,26 @@ class WanVideoPipeline:
         self.use_unified_sequence_parallel = True
 
     # ---------------------------------------------------------------- helpers
-    def check_resize_height_width(self, height, width, num_frames=None):
-        """utils/__init__.py:43-57."""
+    def latent_geometry(self, output_type=None):
+        """(latent channels, spatial stride) of the loaded models: the VAE's when there is one, otherwise
+        the DiT's out_dim -- 16 channels at stride 8 (Wan2.1 VAE), or 48 at stride 16 (the Wan2.2 VAE of
+        TI2V-5B, wan_video_new.py:583).  output_type: what a __call__ is to return -- when the VAE and the
+        DiT disagree the DiT's latents can be produced ("latents": the DiT's geometry) but not decoded
+        (anything else: RuntimeError)."""
+        dit = self.dit if self.dit is not None else self.dit2
+        z = self.vae.z_dim if self.vae is not None else (dit.out_dim if dit is not None else 16)
+        if output_type is not None and self.vae is not None and dit is not None and dit.out_dim != z:
+            if output_type != "latents":
+                raise RuntimeError(f"the loaded VAE decodes {z}-channel latents, the DiT produces {dit.out_dim}: "
+                                   f"use output_type=\"latents\"")
+            z = dit.out_dim
+        return (48, 16) if z == 48 else (16, 8)
+
+    def check_resize_height_width(self, height, width, num_frames=None, output_type=None):
+        """utils/__init__.py:43-57; height / width round up to twice the latent stride when that is 16
+        (wan_video_new.py:399-400: 32).  output_type: as latent_geometry."""
+        if self.latent_geometry(output_type)[1] == 16:
+            height, width = (height + 31) // 32 * 32, (width + 31) // 32 * 32
         if height % self.height_division_factor != 0:
             height = (height + self.height_division_factor - 1) // self.height_division_factor * self.height_division_factor
         if width % self.width_division_factor != 0:
@@ -619,8 +662,13 @@ class WanVideoPipeline:
     def denoise(self, latents, context_posi, context_nega, vace_context=None, vace_scale=1.0, cfg_scale=5.0,
                 num_inference_steps=50, sigma_shift=5.0, denoising_strength=1.0, progress_bar_cmd=None,
                 use_graph=None, tea_cache=None, sliding_window_size=None, sliding_window_stride=None,
-                switch_DiT_boundary=0.875, y=None, clip_feature=None):
+                switch_DiT_boundary=0.875, y=None, clip_feature=None, first_frame_latents=None):
         """The loop of wan_video_new.py:515-542 (cfg_merge batched), returns the final latents.
+
+        first_frame_latents [1, C, 1, h, w] (a fuse_vae_embedding_in_latents DiT, Wan2.2-TI2V-5B): the
+        clean latents of the first frame.  Written into frame 0 of the start latents (:747), every forward
+        runs with fuse_vae_embedding_in_latents=True (frame 0's tokens at timestep 0) and frame 0 is set
+        back to them after each scheduler step (:541-542), inside the captured step too.
 
         y / clip_feature: the image conditioning of an I2V DiT (model_fn_wan_video), constant over the
         steps and handed to both experts; y is cut per window once, like the vace_context.
@@ -653,6 +701,9 @@ class WanVideoPipeline:
         window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context,
                                         tea_cache, y=y)
         image_kw = self._image_kwargs(y, clip_feature)
+        ffl = self._first_frame(first_frame_latents, latents)
+        if ffl is not None:
+            image_kw["fuse_vae_embedding_in_latents"] = True
         self.scheduler.set_timesteps(num_inference_steps, denoising_strength=denoising_strength, shift=sigma_shift)
         n_steps = len(self.scheduler.timesteps)
         segments = plan_experts(self.scheduler.timesteps, switch_DiT_boundary, has2)
@@ -662,6 +713,8 @@ class WanVideoPipeline:
         use_graph = use_graph and tea_cache is None and \
             (not self.use_unified_sequence_parallel or sp_graph_ok(self.sp_group))
         latents = latents.to(device=self.device, dtype=BF16).contiguous().clone()
+        if ffl is not None:
+            latents[:, :, 0:1].copy_(ffl)                                                # :747
         ts = self.scheduler.timesteps.to(dtype=BF16).to(self.device)                     # :526
         ds = torch.tensor([self.scheduler.delta(i) for i in range(n_steps)], dtype=torch.float32,
                           device=self.device)
@@ -680,6 +733,8 @@ class WanVideoPipeline:
                                   use_unified_sequence_parallel=self.use_unified_sequence_parallel,
                                   sp_group=self.sp_group, tea_cache=tea_cache, **window_kw, **image_kw)
                 K.cfg_euler_dev(v[0:1], v[1:2] if use_cfg else None, latents, scale, d_buf)
+                if ffl is not None:
+                    latents[:, :, 0:1].copy_(ffl)                                        # :541-542
             return step
 
         plan = None
@@ -704,6 +759,21 @@ class WanVideoPipeline:
         self.last_graphs = [steppers[first].graph for first, _, _ in segments]
         self.last_graph = self.last_graphs[-1]
         return latents
+
+    def _first_frame(self, first_frame_latents, latents):
+        """first_frame_latents= of denoise as a device bf16 [1, C, 1, h, w] tensor (None without)."""
+        if first_frame_latents is None:
+            return None
+        dit = self.dit
+        if dit is None or not (dit.fuse_vae_embedding_in_latents and dit.seperated_timestep):
+            raise ValueError("first_frame_latents needs a DiT with fuse_vae_embedding_in_latents and "
+                             "seperated_timestep (Wan2.2-TI2V-5B)")
+        if self.dit2 is not None:
+            raise NotImplementedError("first_frame_latents with a second expert (dit2) is not supported")
+        want = (1, latents.shape[1], 1) + tuple(latents.shape[3:])
+        if tuple(first_frame_latents.shape) != want:
+            raise ValueError(f"first_frame_latents: expected {want}, got {tuple(first_frame_latents.shape)}")
+        return first_frame_latents.to(device=self.device, dtype=BF16).contiguous()
 
     def _image_kwargs(self, y, clip_feature):
         """model_fn's image-conditioning arguments as device bf16 tensors ({} without them)."""
@@ -735,7 +805,7 @@ class WanVideoPipeline:
                       cfg_scale=1.2, num_inference_steps=4, sigma_shift=2.0, slg_blocks=(), slg_range=(0.2, 0.7),
                       progress_bar_cmd=None, input_latents=None, forward_step=None, skip_backward_step=None,
                       sliding_window_size=None, sliding_window_stride=None, switch_DiT_boundary=0.875,
-                      y=None, clip_feature=None):
+                      y=None, clip_feature=None, first_frame_latents=None):
         """Config 5's sampler (ditto_comfyui_workflow.json WanVideoSampler 4 / 1.2 / 2.0 / unipc with
         WanVideoSLG): FlowUniPCMultistepScheduler (vstyler.unipc) on fp32 latents, CFG as one
         batch-2 forward, skip-layer guidance on the uncond sample for step fractions in slg_range.
@@ -755,6 +825,8 @@ class WanVideoPipeline:
         touched: the Wan2.2 enhancer pass (40 steps, shift 12, forward_step = skip_backward_step = 5)
         has every timestep below 875 and runs with pipe.dit = None."""
         from .experts import expert_cfg_scales, plan_experts
+        if first_frame_latents is not None:
+            raise ValueError("first_frame_latents is not supported by the UniPC sampler (use denoise)")
         has2 = self.dit2 is not None
         scales = expert_cfg_scales(cfg_scale, has2)
         window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context,
@@ -818,8 +890,12 @@ class WanVideoPipeline:
                  tea_cache_model_id="", progress_bar_cmd=None,
                  # extensions of this build (the DiT path without T5/VAE):
                  prompt_emb=None, negative_prompt_emb=None, vace_context=None, output_type="video",
-                 input_latents=None, clip_feature=None, **kwargs):
-        """wan_video_new.py:416-560 for the Ditto path (T2V/VACE/video-to-video) and image-to-video (no
+                 input_latents=None, clip_feature=None, first_frame_latents=None, **kwargs):
+        """first_frame_latents [1, C, 1, h, w]: the clean first-frame latents of a
+        fuse_vae_embedding_in_latents DiT (Wan2.2-TI2V-5B image-to-video; denoise).  input_image= on such a
+        DiT needs the 48-channel Wan2.2 VAE, which this build does not have.
+
+        wan_video_new.py:416-560 for the Ditto path (T2V/VACE/video-to-video) and image-to-video (no
         audio/camera inputs).  input_image (and end_image) on a DiT with in_dim > 16 become y
         (encode_input_image) for both experts; a DiT that also takes CLIP features (has_image_input with
         require_clip_embedding: the Wan2.1 I2V / FLF2V / Fun-InP checkpoints) gets them from
@@ -830,6 +906,13 @@ class WanVideoPipeline:
         of the shortened schedule (WanVideoUnit_InputVideoEmbedder, :591-614)."""
         if motion_bucket_id is not None:
             raise NotImplementedError("motion_bucket_id is outside the Ditto hot path of this build")
+        fused = self.dit is not None and self.dit.fuse_vae_embedding_in_latents
+        if input_image is not None and fused:
+            raise NotImplementedError("input_image on a fuse_vae_embedding_in_latents DiT (Wan2.2-TI2V-5B) needs the "
+                                      "48-channel Wan2.2 VAE, which this build does not have: pass the encoded "
+                                      "first frame as first_frame_latents=")
+        if first_frame_latents is not None and not fused:
+            raise ValueError("first_frame_latents needs a DiT with fuse_vae_embedding_in_latents (Wan2.2-TI2V-5B)")
         self._check_image_args(input_image, end_image, clip_feature)
         if input_video is not None and input_latents is not None:
             raise ValueError("pass input_video or its precomputed input_latents, not both")
@@ -838,8 +921,9 @@ class WanVideoPipeline:
         scales = expert_cfg_scales(cfg_scale, self.dit2 is not None)
         if tea_cache_l1_thresh is not None and self.dit2 is not None:
             raise NotImplementedError("tea_cache_l1_thresh with a second expert (dit2) is not supported")
-        height, width, num_frames = self.check_resize_height_width(height, width, num_frames)
+        height, width, num_frames = self.check_resize_height_width(height, width, num_frames, output_type)
         T = (num_frames - 1) // 4 + 1
+        zc, zs = self.latent_geometry(output_type)
         # WanVideoUnit_NoiseInitializer (wan_video_new.py:578-587): f reference images add f latent
         # frames, and the noise is rolled so the last f frames come first
         nref = 0
@@ -848,7 +932,7 @@ class WanVideoPipeline:
         if input_video is not None or input_latents is not None:
             input_latents = self.encode_input_video(input_video, input_latents, height, width, num_frames, tiled,
                                                     tile_size, tile_stride, vace_reference_image)
-        noise = self.generate_noise((1, 16, T + nref, height // 8, width // 8), seed=seed, rand_device=rand_device)
+        noise = self.generate_noise((1, zc, T + nref, height // zs, width // zs), seed=seed, rand_device=rand_device)
         if nref:
             noise = torch.cat((noise[:, :, -nref:], noise[:, :, :-nref]), dim=2)
         start = noise
@@ -879,7 +963,7 @@ class WanVideoPipeline:
                                cfg_scale, num_inference_steps, sigma_shift, denoising_strength, progress_bar_cmd,
                                tea_cache=tea_cache, sliding_window_size=sliding_window_size,
                                sliding_window_stride=sliding_window_stride, switch_DiT_boundary=switch_DiT_boundary,
-                               y=y, clip_feature=clip_feature)
+                               y=y, clip_feature=clip_feature, first_frame_latents=first_frame_latents)
         self.last_tea_cache = tea_cache
         if nref:                                            # :545-550
             latents = latents[:, :, nref:].contiguous()
@@ -894,7 +978,7 @@ class WanVideoPipeline:
     def enhance(self, video, prompt=None, negative_prompt="", height=720, width=1280, num_inference_steps=40,
                 sigma_shift=12.0, cfg_scale=(3.0, 4.0), switch_DiT_boundary=0.875, forward_step=5,
                 skip_backward_step=5, seed=None, tiled=True, tile_size=(30, 52), tile_stride=(15, 26),
-                prompt_emb=None, negative_prompt_emb=None, output_type="video"):
+                prompt_emb=None, negative_prompt_emb=None, output_type="video", first_frame_latents=None):
         """The reference's "Denoising Enhancing" mode (denoising_enhancing/video_enhancing_batch.py:43-83,
         395-419 around wan/text2video.py:297-401 with wan/configs/wan_t2v_A14B.py): frames in, frames
         out.  The video is resized to height x width (nearest neighbour, vs_resize_nearest_u8, when it is
@@ -917,6 +1001,8 @@ class WanVideoPipeline:
         output_type: "video" (PIL images), "u8" ((T, H, W, 3) uint8 device tensor) or "latents"."""
         from .experts import expert_cfg_scales
         from .vae import frames_to_u8, preprocess_video
+        if first_frame_latents is not None:
+            raise ValueError("first_frame_latents is not supported by enhance (the UniPC sampler)")
         frames = frames_to_u8(video, self.device)
         if frames.shape[0] % 4 != 1:
             raise ValueError(f"enhance: the video must have 4k + 1 frames, got {frames.shape[0]}")

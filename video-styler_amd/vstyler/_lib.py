@@ -1,5 +1,5 @@
 """ctypes binding of libvstyler.so (the C ABI declared in include/vstyler.h, vstyler_image.h,
-vstyler_clip.h and vstyler_seg.h).
+vstyler_clip.h, vstyler_seg.h and vstyler_control.h).
 
 The product path has no CPU fallback: if the library is missing every op raises.
 """
@@ -134,6 +134,15 @@ SIGNATURES_SEG = {
     "vs_layernorm_modulate_seg": [_P, _LL, _P, _LL, _I, _I, _I, _I, _P, _P, _LL, _P, _P, _F, _P],
     "vs_layernorm_modulate_fp8_seg": [_P, _LL, _P, _LL, _P, _I, _I, _I, _I, _P, _P, _LL, _P, _P, _F, _P],
 }
+# Wan-Fun control: reference-image rows, camera rays and the adapter's im2col (include/vstyler_control.h):
+# a fifth table
+SIGNATURES_CONTROL = {
+    "vs_ref_rows": [_P, _LL, _P, _LL, _I, _I, _I, _I, _P],
+    "vs_unpatchify_skip": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vs_camera_rays": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "vs_camera_im2col": [_P, _P, _LL, _I, _I, _I, _I, _P],
+    "vs_relu": [_P, _LL, _P],
+}
 _RESTYPES = {"vs_strerror": ctypes.c_char_p, "vs_split_workspace_bytes": ctypes.c_longlong,
              "vs_sp_last_error": ctypes.c_char_p}
 
@@ -150,7 +159,8 @@ def load():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or make -C video-styler_amd/csrc)")
         lib = ctypes.CDLL(LIB_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(SIGNATURES_IMAGE.items()) +
-                               list(SIGNATURES_CLIP.items()) + list(SIGNATURES_SEG.items())):
+                               list(SIGNATURES_CLIP.items()) + list(SIGNATURES_SEG.items()) +
+                               list(SIGNATURES_CONTROL.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, ctypes.c_int)

@@ -438,6 +438,75 @@ def unpatchify(tokens, out):
     return out
 
 
+def unpatchify_skip(tokens, out, skip):
+    """unpatchify whose sample b reads its S rows behind `skip` prepended ones: tokens is
+    [B * (skip + S), 4 C] (vs_unpatchify_skip; skip 0 is unpatchify)."""
+    _req(out, "out"), _req(tokens, "tokens")
+    B, C, T, H, W = out.shape
+    S = T * (H // 2) * (W // 2)
+    if skip < 0 or not tokens.is_contiguous() or not out.is_contiguous() or tokens.dim() != 2 or \
+            tuple(tokens.shape) != (B * (skip + S), 4 * C):
+        raise ValueError(f"unpatchify_skip: tokens {tuple(tokens.shape)} are not [{B} * ({skip} + {S}), {4 * C}]")
+    _lib.check(_lib.load().vs_unpatchify_skip(tokens.data_ptr(), out.data_ptr(), B, C, T, H, W, int(skip),
+                                              _stream(out)))
+    return out
+
+
+def ref_rows(src, dst, batch, n, s):
+    """dst [batch * (n + s), D]: the first n rows of every sample = src's ([n, D]: one set for all, or
+    [batch * n, D]); no other row is written (vs_ref_rows)."""
+    Ms, D, lds = _rows(src, "src")
+    Md, Dd, ldd = _rows(dst, "dst")
+    if Dd != D or lds != D or Ms not in (n, batch * n) or Md != batch * (n + s):
+        raise ValueError(f"ref_rows: src {tuple(src.shape)} / dst {tuple(dst.shape)} against batch {batch}, "
+                         f"{n} + {s} rows")
+    _lib.check(_lib.load().vs_ref_rows(src.data_ptr(), 0 if Ms == n and batch > 1 else n * D, dst.data_ptr(), ldd,
+                                       batch, n, s, D, _stream(dst)))
+    return dst
+
+
+def camera_rays(intrinsics, c2w, out):
+    """out bf16 [24, T, H, W]: the Pluecker rays of the pixel frames, grouped in fours
+    (vs_camera_rays).  intrinsics fp32 [F, 4], c2w fp32 [F, 3, 4], F >= 4 T - 3."""
+    _req(out, "out")
+    if out.dim() != 4 or out.shape[0] != 24 or not out.is_contiguous():
+        raise ValueError(f"camera_rays: out must be a contiguous [24, T, H, W] tensor, got {tuple(out.shape)}")
+    F = intrinsics.shape[0]
+    for t, name, shape in ((intrinsics, "intrinsics", (F, 4)), (c2w, "c2w", (F, 3, 4))):
+        if t.dtype != torch.float32 or t.device != out.device or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"camera_rays: {name} must be contiguous float32 {shape} on {out.device}")
+    _, T, H, W = out.shape
+    if F < 4 * T - 3:
+        raise ValueError(f"camera_rays: {F} pixel frames for {T} latent frames (at least {4 * T - 3})")
+    _lib.check(_lib.load().vs_camera_rays(intrinsics.data_ptr(), c2w.data_ptr(), out.data_ptr(), F, T, H, W,
+                                          _stream(out)))
+    return out
+
+
+def camera_im2col(x, out):
+    """x [C, T, H, W] -> out [T (H/16) (W/16), 256 C]: PixelUnshuffle(8) + the 2x2 / stride 2 unfold
+    (vs_camera_im2col)."""
+    _req(x, "x")
+    if x.dim() != 4 or not x.is_contiguous() or x.shape[2] % 16 or x.shape[3] % 16:
+        raise ValueError(f"camera_im2col: x must be a contiguous [C, T, H, W] tensor with H, W multiples of 16, "
+                         f"got {tuple(x.shape)}")
+    C, T, H, W = x.shape
+    rows, cols, ldo = _rows(out, "out")
+    if rows != T * (H // 16) * (W // 16) or cols != 256 * C:
+        raise ValueError(f"camera_im2col: out {tuple(out.shape)} is not [{T * (H // 16) * (W // 16)}, {256 * C}]")
+    _lib.check(_lib.load().vs_camera_im2col(x.data_ptr(), out.data_ptr(), ldo, C, T, H, W, _stream(x)))
+    return out
+
+
+def relu(x):
+    """x = max(x, 0) in place (vs_relu)."""
+    _req(x, "x")
+    if not x.is_contiguous() or x.numel() % 8:
+        raise ValueError("relu: a contiguous tensor of a multiple of 8 elements required")
+    _lib.check(_lib.load().vs_relu(x.data_ptr(), x.numel(), _stream(x)))
+    return x
+
+
 def cfg_euler(v_pos, v_neg, x, cfg_scale, dsigma):
     for t, n in ((v_pos, "v_pos"), (x, "x")):
         _req(t, n)

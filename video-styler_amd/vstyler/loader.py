@@ -39,6 +39,25 @@ WAN_TI2V_DIT_CONFIGS = {
                                              require_clip_embedding=False, require_vae_embedding=False,
                                              fuse_vae_embedding_in_latents=True),
 }
+# Wan-Fun control (wan_video_dit.py:580-594, 610-677, 713-748): control latents in y (in_dim 48 / 52), the
+# reference image's ref_conv, the camera control_adapter (in_dim 32 / 36).  A fourth table, looked up after
+# the three above.
+_B13 = dict(dim=1536, ffn_dim=8960, num_heads=12, num_layers=30)
+_B14 = dict(dim=5120, ffn_dim=13824, num_heads=40, num_layers=40)
+WAN_FUN_DIT_CONFIGS = {
+    "efa44cddf936c70abd0ea28b6cbe946c": dict(_B14, in_dim=48, has_image_input=True),         # 14B control v1.0
+    "70ddad9d3a133785da5ea371aae09504": dict(_B13, in_dim=48, has_image_input=True, has_ref_conv=True),   # 1.3B v1.1
+    "26bde73488a92e64cc20b0a7485b9e5b": dict(_B14, in_dim=48, has_image_input=True, has_ref_conv=True),   # 14B v1.1
+    "ac6a5aa74f4a0aab6f64eb9a72f19901": dict(_B13, in_dim=32, has_image_input=True, add_control_adapter=True,
+                                             in_dim_control_adapter=24),                     # 1.3B camera v1.1
+    "b61c605c2adbd23124d152ed28e049ae": dict(_B14, in_dim=32, has_image_input=True, add_control_adapter=True,
+                                             in_dim_control_adapter=24),                     # 14B camera v1.1
+    "2267d489f0ceb9f21836532952852ee5": dict(_B14, in_dim=52, has_image_input=False, has_ref_conv=True,
+                                             require_clip_embedding=False),                  # Wan2.2-Fun-A14B-Control
+    "47dbeab5e560db3180adf51dc0232fb1": dict(_B14, in_dim=36, has_image_input=False, add_control_adapter=True,
+                                             in_dim_control_adapter=24,
+                                             require_clip_embedding=False),           # Wan2.2-Fun-A14B-Control-Camera
+}
 WAN_COMMON = dict(in_dim=16, out_dim=16, text_dim=4096, freq_dim=256, eps=1e-6, patch_size=(1, 2, 2))
 VACE_14B_HASH = "3b2726384e4f64837bdf216eea3f310d"
 VACE_14B = dict(vace_layers=(0, 5, 10, 15, 20, 25, 30, 35), vace_in_dim=96, patch_size=(1, 2, 2),
@@ -192,7 +211,12 @@ def dit_config_from_shapes(sd):
         return None
     dim = pe.shape[0]
     image = "blocks.0.cross_attn.k_img.weight" in sd
-    return dict(WAN_COMMON, has_image_input=image, has_image_pos_emb="img_emb.emb_pos" in sd,
+    control = {}
+    if "ref_conv.weight" in sd:
+        control["has_ref_conv"] = True
+    if "control_adapter.conv.weight" in sd:     # Conv2d(64 in_dim_control_adapter, dim, 2, 2)
+        control.update(add_control_adapter=True, in_dim_control_adapter=sd["control_adapter.conv.weight"].shape[1] // 64)
+    return dict(WAN_COMMON, **control, has_image_input=image, has_image_pos_emb="img_emb.emb_pos" in sd,
                 require_clip_embedding=image, dim=dim, in_dim=pe.shape[1], ffn_dim=sd["blocks.0.ffn.0.weight"].shape[0],
                 num_heads=dim // 128, num_layers=_n_blocks(sd, "blocks"),
                 text_dim=sd["text_embedding.0.weight"].shape[1], freq_dim=sd["time_embedding.0.weight"].shape[1],
@@ -213,8 +237,9 @@ def vace_config_from_shapes(sd, num_layers):
 def build_dit(state_dict, device):
     sd = {k: v for k, v in state_dict.items() if not k.startswith("vace")}
     h = hash_state_dict_keys(sd)
-    if h in WAN_DIT_CONFIGS or h in WAN_I2V_DIT_CONFIGS or h in WAN_TI2V_DIT_CONFIGS:
-        cfg = dict(WAN_COMMON, **(WAN_DIT_CONFIGS.get(h) or WAN_I2V_DIT_CONFIGS.get(h) or WAN_TI2V_DIT_CONFIGS[h]))
+    tables = (WAN_DIT_CONFIGS, WAN_I2V_DIT_CONFIGS, WAN_TI2V_DIT_CONFIGS, WAN_FUN_DIT_CONFIGS)
+    if any(h in t for t in tables):
+        cfg = dict(WAN_COMMON, **next(t[h] for t in tables if h in t))
     else:
         cfg = dit_config_from_shapes(sd)
         if cfg is None:

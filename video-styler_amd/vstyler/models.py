@@ -203,25 +203,38 @@ class PatchEmbed(nn.Module):
             self._wpad, self._wpad_of = wp, key
         return self._wpad
 
-    def forward(self, lat, ws, tag, y=None, batch=None):
+    def forward(self, lat, ws, tag, y=None, batch=None, skip=0, residual=None):
         """lat [B, C, T, H, W] -> tokens [B*S, dim].  y [B or 1, in_dim - C, T, H, W]: the channels
         concatenated behind lat's (wan_video_new.py:1367-1368), read in place by vs_patchify2; with y
         (or with 4 in_dim no multiple of 64) the token rows and the weight are K-padded.  batch: the
-        output samples when lat and y are batch-1 operands broadcast over the CFG batch."""
+        output samples when lat and y are batch-1 operands broadcast over the CFG batch.
+
+        residual [B*S, dim]: added in the GEMM's epilogue, bf16(residual + bf16(acc + bias)) (the camera
+        adapter's output, wan_video_dit.py:341-344).  skip > 0: the output is [B*(skip + S), dim] and sample
+        b's tokens are its rows skip.. (the rows in front are the caller's: the reference image's tokens),
+        written by one GEMM per sample through a row view."""
         B, C, T, H, W = lat.shape
         S = T * (H // 2) * (W // 2)
+        epi = {} if residual is None else dict(epilogue=K.VS_EPI_RES, residual=residual)
         if y is None and batch is None and (C * 4) % 64 == 0:
             cols = ws.get(tag + ".cols", (B * S, C * 4))
             K.patchify(lat.contiguous(), cols)
+            w = self.weight.view(self.dim, C * 4)
+        else:
+            B = B if batch is None else batch
+            w = self.padded_weight()
+            cols = ws.get(tag + ".cols", (B * S, w.shape[1]))
+            K.patchify2(lat.contiguous(), None if y is None else y.contiguous(), cols)
+        if not skip:
             out = ws.get(tag + ".out", (B * S, self.dim))
-            K.gemm(cols, self.weight.view(self.dim, C * 4), out, bias=self.bias)
+            K.gemm(cols, w, out, bias=self.bias, **epi)
             return out, (T, H // 2, W // 2)
-        B = B if batch is None else batch
-        wp = self.padded_weight()
-        cols = ws.get(tag + ".cols", (B * S, wp.shape[1]))
-        K.patchify2(lat.contiguous(), None if y is None else y.contiguous(), cols)
-        out = ws.get(tag + ".out", (B * S, self.dim))
-        K.gemm(cols, wp, out, bias=self.bias)
+        R = skip + S
+        out = ws.get(tag + ".out", (B * R, self.dim))
+        for b in range(B):
+            if residual is not None:
+                epi["residual"] = residual[b * S:(b + 1) * S]
+            K.gemm(cols[b * S:(b + 1) * S], w, out[b * R + skip:(b + 1) * R], bias=self.bias, **epi)
         return out, (T, H // 2, W // 2)
 
 
@@ -698,6 +711,87 @@ class ImgEmb(nn.Module):
             self.emb_pos = _param(1, 2 * IMG_TOKENS, in_dim, device=device)
 
 
+class RefConv(nn.Module):
+    """Conv2d(16, dim, k = s = 2) parameters (wan_video_dit.py:331): the reference image's latents -> tokens."""
+
+    def __init__(self, dim, device=None):
+        super().__init__()
+        self.weight = _param(dim, 16, 2, 2, device=device)
+        self.bias = _param(dim, device=device)
+
+
+class Conv2dParams(nn.Module):
+    def __init__(self, cin, cout, k, device=None):
+        super().__init__()
+        self.weight = _param(cout, cin, k, k, device=device)
+        self.bias = _param(cout, device=device)
+
+
+class AdapterResidualBlock(nn.Module):
+    """ResidualBlock(dim) parameters (wan_video_camera_controller.py:63-75): two 3x3 convs, padding 1."""
+
+    def __init__(self, dim, device=None):
+        super().__init__()
+        self.conv1 = Conv2dParams(dim, dim, 3, device)
+        self.conv2 = Conv2dParams(dim, dim, 3, device)
+
+
+class SimpleAdapter(nn.Module):
+    """The camera control adapter (wan_video_camera_controller.py:8-44) under the reference's parameter
+    names: PixelUnshuffle(8), conv = Conv2d(64 in_dim, dim, k = s = 2), one ResidualBlock.  forward runs on
+    token rows: the [T h w, dim] buffer is the 3x3 convs' channels-last layout with n = T frames."""
+
+    def __init__(self, in_dim, out_dim, device=None, num_residual_blocks=1):
+        super().__init__()
+        if num_residual_blocks != 1:
+            raise NotImplementedError("SimpleAdapter: one residual block (every published layout)")
+        self.in_dim, self.out_dim = in_dim, out_dim
+        self.conv = Conv2dParams(in_dim * 64, out_dim, 2, device)
+        self.residual_blocks = nn.ModuleList([AdapterResidualBlock(out_dim, device)])
+        self._cw = {}
+
+    def _conv_weight(self, name, conv):
+        """The 3x3 weight re-laid out for vs_vae_conv (vae.ConvW), once per loaded weight."""
+        from .vae import ConvW
+        key = (conv.weight.data_ptr(), conv.weight._version, conv.bias.data_ptr(), conv.bias._version)
+        have = self._cw.get(name)
+        if have is None or have[0] != key:
+            have = (key, ConvW(conv.weight, conv.bias, conv.weight.device))
+            self._cw[name] = have
+        return have[1]
+
+    def forward(self, control_camera_latents_input):
+        """[1, in_dim, T, H, W] (H, W pixels) -> [T (H/16)(W/16), dim] token rows, in the patch embedding's
+        row order: SimpleAdapter.forward's x_conv, relu(conv1), conv2 + bias, += residual, each a bf16
+        tensor as the reference's bf16 modules make them.  Once per call, outside the captured step: the
+        buffers are the caller's (the im2col is 400 MB at 832x480x81), not the Workspace's."""
+        from .vae import conv as vae_conv
+        x = control_camera_latents_input
+        if x.dim() != 5 or x.shape[0] != 1 or x.shape[1] != self.in_dim or x.shape[3] % 16 or x.shape[4] % 16:
+            raise ValueError(f"control_camera_latents_input: expected [1, {self.in_dim}, T, H, W] with H, W multiples "
+                             f"of 16, got {tuple(x.shape)}")
+        _, C, T, H, W = x.shape
+        h, w, D = H // 16, W // 16, self.out_dim
+        M = T * h * w
+        dev = self.conv.weight.device
+
+        def buf(cols):
+            return torch.empty((M, cols), device=dev, dtype=BF16)
+        cols = buf(256 * C)
+        K.camera_im2col(x.to(device=dev, dtype=BF16).contiguous()[0], cols)
+        u = buf(D)
+        K.gemm(cols, self.conv.weight.view(D, 256 * C), u, bias=self.conv.bias)
+        blk = self.residual_blocks[0]
+        a = buf(D)
+        vae_conv(u.view(T, 1, h, w, D), self._conv_weight("conv1", blk.conv1), (1, h, w), pad=(0, 1, 1),
+                 y=a.view(T, 1, h, w, D))
+        K.relu(a)
+        out = buf(D)
+        vae_conv(a.view(T, 1, h, w, D), self._conv_weight("conv2", blk.conv2), (1, h, w), pad=(0, 1, 1),
+                 y=out.view(T, 1, h, w, D), res=u.view(T, 1, h, w, D))
+        return out
+
+
 CLIP_DIM = 1280       # clip_feature_dim (wan_video_dit.py:322)
 IMG_EMB_EPS = 1e-5    # nn.LayerNorm's default eps, which MLP.proj's two LayerNorms keep
 
@@ -707,17 +801,24 @@ class WanModel(nn.Module):
     in_dim > 16 (the VAE-embedded image `y` concatenated behind the latents: I2V, FLF2V, Fun-InP,
     Wan2.2-I2V-A14B; or the 48 latent channels of Wan2.2-TI2V-5B, which takes no `y`:
     fuse_vae_embedding_in_latents / seperated_timestep) with or without the CLIP image branch (has_image_input: img_emb + the blocks'
-    k_img / v_img / norm_k_img; has_image_pos_emb: img_emb.emb_pos over 514 tokens)."""
+    k_img / v_img / norm_k_img; has_image_pos_emb: img_emb.emb_pos over 514 tokens).  The Wan-Fun control
+    layouts (in_dim > 16, out_dim 16) add has_ref_conv (ref_conv: the reference image's latents -> tokens in
+    front of the sequence) and add_control_adapter (control_adapter: the camera rays -> rows added to the patch
+    embedding's), :330-345."""
 
     def __init__(self, dim, in_dim, ffn_dim, out_dim, text_dim, freq_dim, eps, patch_size, num_heads,
                  num_layers, has_image_input=False, has_image_pos_emb=False, has_ref_conv=False,
                  add_control_adapter=False, seperated_timestep=False, require_vae_embedding=True,
-                 require_clip_embedding=True, fuse_vae_embedding_in_latents=False, device=None, **kwargs):
+                 require_clip_embedding=True, fuse_vae_embedding_in_latents=False, in_dim_control_adapter=24,
+                 device=None, **kwargs):
         super().__init__()
         for name, on in (("has_ref_conv", has_ref_conv), ("add_control_adapter", add_control_adapter)):
-            if on:
+            # ref_conv reads 16-channel Wan2.1 latents and every Fun-Control layout keeps the control / image
+            # channels in y: in_dim > 16 with 16 output channels (wan_video_dit.py:610-748)
+            if on and not (in_dim > 16 and out_dim == 16):
                 raise NotImplementedError(f"WanModel({name}=True) (Fun-Control reference conv, camera control) "
-                                          f"is not in this build")
+                                          f"with in_dim {in_dim} / out_dim {out_dim} is not in this build: the "
+                                          f"Fun-Control layouts have in_dim > 16 and out_dim 16")
         if bool(seperated_timestep) != bool(fuse_vae_embedding_in_latents):
             # Wan2.2-TI2V-5B, the one layout with either flag, sets both; each alone is another model
             raise NotImplementedError("WanModel: seperated_timestep and fuse_vae_embedding_in_latents go together "
@@ -749,7 +850,23 @@ class WanModel(nn.Module):
         self.head = Head(dim, out_dim, patch_size, eps, device)
         if has_image_input:
             self.img_emb = ImgEmb(CLIP_DIM, dim, has_pos_emb=has_image_pos_emb, device=device)
+        # Wan-Fun control (wan_video_dit.py:330-337): the reference image's tokens, the camera adapter
+        self.has_ref_conv = bool(has_ref_conv)
+        if has_ref_conv:
+            self.ref_conv = RefConv(dim, device)
+        self.control_adapter = SimpleAdapter(in_dim_control_adapter, dim, device) if add_control_adapter else None
         self._rope = None
+
+    def ref_tokens(self, reference_latents, ws):
+        """reference_latents [Br, 16, h, w] -> [Br * (h/2)(w/2), D]: ref_conv(...).flatten(2).transpose(1, 2)
+        (wan_video_new.py:1388) as the im2col of one frame and one GEMM with bias, the conv's rounding."""
+        Br, C, H, W = reference_latents.shape
+        n = (H // 2) * (W // 2)
+        cols = ws.get("ref.cols", (Br * n, 4 * C))
+        K.patchify(reference_latents.to(device=self.ref_conv.weight.device, dtype=BF16).contiguous().view(Br, C, 1, H, W),
+                   cols)
+        out = ws.get("ref.out", (Br * n, self.dim))
+        return K.gemm(cols, self.ref_conv.weight.view(self.dim, 4 * C), out, bias=self.ref_conv.bias)
 
     def img_embed(self, clip_feature, ws):
         """clip_feature [Bc, N, 1280] -> [Bc*N, D]: MLP.forward (wan_video_dit.py:246-249) as

@@ -31,8 +31,8 @@ def _workspace(device):
     return _WS[key]
 
 
-_UNSUPPORTED = ("reference_latents", "audio_embeds", "motion_latents", "s2v_pose_latents",
-                "motion_bucket_id", "pose_latents", "face_pixel_values", "control_camera_latents_input")
+_UNSUPPORTED = ("audio_embeds", "motion_latents", "s2v_pose_latents", "motion_bucket_id", "pose_latents",
+                "face_pixel_values")
 
 _WINDOW_PLANS = {}
 
@@ -101,7 +101,8 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
                        vace_context=None, vace_scale=1.0, use_unified_sequence_parallel: bool = False,
                        sp_group=None, slg_blocks=(), tea_cache=None, cfg_sample=0, sliding_window_size=None,
                        sliding_window_stride=None, vace_context_windows=None, y=None, clip_feature=None,
-                       y_windows=None, fuse_vae_embedding_in_latents=False, **kwargs):
+                       y_windows=None, fuse_vae_embedding_in_latents=False, reference_latents=None,
+                       control_camera_latents_input=None, reference_tokens=None, camera_tokens=None, **kwargs):
     """One DiT(+VACE) forward (wan_video_new.py:1338-1468) -> [B,dit.out_dim,T,H,W] bf16 velocity.
 
     fuse_vae_embedding_in_latents (with dit.seperated_timestep: Wan2.2-TI2V-5B's image-to-video mode,
@@ -137,7 +138,35 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     dit.has_image_input; the first 257 embedded rows are the blocks' image keys, any further rows join
     the text keys (wan_video_dit.py:172-174).  A DiT with in_dim > 16 needs y and one with
     has_image_input needs clip_feature: ValueError otherwise (the reference would feed the patch
-    embedding too few channels / attend to the first 257 text rows as the image)."""
+    embedding too few channels / attend to the first 257 text rows as the image).
+
+    Wan-Fun control.  reference_latents [1 or B, 16, (1,) H, W] on a has_ref_conv DiT (:1384-1390,
+    :1463-1466): dit.ref_conv turns them into n = (H/2)(W/2) tokens in front of every sample's S: the
+    forward is the ordinary one over the grid (T + 1, H/2, W/2) whose frame 0 comes from ref_conv, and the
+    head's rows n.. are unpatchified.  control_camera_latents_input [1, 24, T, 8 H, 8 W] on a DiT with
+    control_adapter (wan_video_dit.py:339-345): the adapter's output is added to the patch embedding's in
+    that GEMM's epilogue.  Neither depends on the timestep: a denoising loop computes them once
+    (reference_token_rows, camera_token_rows) and hands them over as reference_tokens [Br n, D] /
+    camera_tokens [S or B S, D], which win over the raw inputs.  ValueError: a DiT without the module, a
+    wrong shape, reference_latents together with a VACE context (the reference's token counts do not
+    match there); NotImplementedError: camera control over more than one sliding window (the reference's
+    tiler drops it, :1292-1307)."""
+    use_ref = reference_latents is not None or reference_tokens is not None
+    use_cam = control_camera_latents_input is not None or camera_tokens is not None
+    if use_ref:
+        if not getattr(dit, "has_ref_conv", False):
+            raise ValueError("model_fn_wan_video: reference_latents needs a DiT with ref_conv (has_ref_conv)")
+        if vace is not None and vace_context is not None:
+            raise ValueError("model_fn_wan_video: reference_latents together with a VACE context (the reference "
+                             "tokens have no VACE rows)")
+        if reference_tokens is None:
+            reference_latents = _reference_frame(reference_latents, latents, context.shape[0])
+    if use_cam:
+        if getattr(dit, "control_adapter", None) is None:
+            raise ValueError("model_fn_wan_video: control_camera_latents_input needs a DiT with control_adapter "
+                             "(add_control_adapter)")
+        if camera_tokens is None:
+            _check_camera_input(dit, control_camera_latents_input, latents)
     for name in _UNSUPPORTED:
         if kwargs.get(name) is not None:
             raise NotImplementedError(f"model_fn_wan_video: '{name}' is outside the Ditto hot path")
@@ -159,11 +188,17 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
             # the reference hands one TeaCache state to every window (:1304), which compares and reuses
             # residuals across different windows
             raise NotImplementedError("model_fn_wan_video: tea_cache with a temporal sliding window")
+        if use_cam:
+            raise NotImplementedError("model_fn_wan_video: control_camera_latents_input with a temporal sliding "
+                                      "window of more than one window")
+        if use_ref and reference_tokens is None:    # the same reference rows in front of every window
+            reference_tokens = reference_token_rows(dit, reference_latents)
         return _windowed_forward(win[0], win[1], dit, motion_controller, vace, animate_adapter, latents, vace_context,
                                  vace_context_windows, y=y, y_windows=y_windows, clip_feature=clip_feature,
                                  timestep=timestep, context=context, vace_scale=vace_scale,
                                  use_unified_sequence_parallel=use_unified_sequence_parallel, sp_group=sp_group,
-                                 slg_blocks=slg_blocks, cfg_sample=cfg_sample, **kwargs)
+                                 slg_blocks=slg_blocks, cfg_sample=cfg_sample, reference_tokens=reference_tokens,
+                                 **kwargs)
     if y is not None and not dit.require_vae_embedding:
         y = y_windows = None
     use_clip = clip_feature is not None and dit.require_clip_embedding and dit.has_image_input
@@ -190,12 +225,18 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
                 def mine(tn):
                     return tn[c:c + 1] if tn is not None and tn.dim() > 0 and tn.shape[0] == 2 else tn
                 ts = timestep.reshape(-1)
+                hw = (latents.shape[3] // 2) * (latents.shape[4] // 2)
                 local = model_fn_wan_video(dit, motion_controller, vace, animate_adapter, latents=mine(latents),
                                            timestep=mine(ts), context=context[c:c + 1],
                                            vace_context=mine(vace_context), vace_scale=vace_scale,
                                            use_unified_sequence_parallel=plan.ulysses is not None,
                                            sp_group=plan.ulysses, slg_blocks=slg_blocks, cfg_sample=c, y=mine(y),
-                                           clip_feature=mine(clip_feature), **kwargs)
+                                           clip_feature=mine(clip_feature),
+                                           reference_latents=mine(reference_latents),
+                                           control_camera_latents_input=control_camera_latents_input,
+                                           reference_tokens=_mine_rows(reference_tokens, c, hw),
+                                           camera_tokens=_mine_rows(camera_tokens, c, latents.shape[2] * hw),
+                                           **kwargs)
                 out = torch.empty((2,) + tuple(local.shape[1:]), device=local.device, dtype=local.dtype)
                 plan.gather_cfg(out, local)
                 return out
@@ -206,6 +247,14 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     # are shared (the cfg_merge broadcast below): the first blocks' self-attention halves are then
     # computed once for all samples (DiTBlock shared_prefix)
     shared = B > 1 and latents.shape[0] == 1 and timestep.numel() == 1 and (y is None or y.shape[0] == 1)
+    ref = n_ref = None
+    if use_ref:
+        ref = reference_tokens if reference_tokens is not None else dit.ref_tokens(reference_latents, ws)
+        n_ref = (latents.shape[3] // 2) * (latents.shape[4] // 2)
+        if ref.dim() != 2 or ref.shape[1] != dit.dim or ref.shape[0] not in (n_ref, B * n_ref):
+            raise ValueError(f"model_fn_wan_video: reference_tokens {tuple(ref.shape)} are not [{n_ref} or "
+                             f"{B} * {n_ref}, {dit.dim}]")
+        shared = shared and ref.shape[0] == n_ref
     shared_vace = shared and vace_context is not None and vace_context.shape[0] == 1
     if y is not None:
         if y.shape[0] not in (1, B) or tuple(y.shape[2:]) != tuple(latents.shape[2:]):
@@ -225,11 +274,31 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
         timestep = torch.stack([torch.zeros_like(timestep), timestep], dim=1).reshape(-1)
     t, t_mod = dit.time_embed(timestep, ws)
     ctx = dit.text_embed(context.to(BF16), ws)
-    if y is None:
+    extra = {}
+    if use_cam:
+        S0 = latents.shape[2] * (latents.shape[3] // 2) * (latents.shape[4] // 2)
+        cam = camera_tokens if camera_tokens is not None else dit.control_adapter(control_camera_latents_input)
+        if cam.dim() != 2 or cam.shape[1] != dit.dim or cam.shape[0] not in (S0, B * S0):
+            raise ValueError(f"model_fn_wan_video: camera_tokens {tuple(cam.shape)} are not [{S0} or {B} * {S0}, "
+                             f"{dit.dim}]")
+        if cam.shape[0] != B * S0:      # (a loop hands the replicated rows: camera_token_rows(batch=B))
+            cam = ws.get("cam_rep", (B * S0, dit.dim)).view(B, S0, dit.dim).copy_(
+                cam.view(1, S0, dit.dim).expand(B, S0, dit.dim)).view(B * S0, dit.dim)
+        extra["residual"] = cam
+    if use_ref:
+        extra["skip"] = n_ref
+    if y is None and not extra:
         x, grid = dit.patch_embedding(latents, ws, "x")
+    elif y is None:
+        x, grid = dit.patch_embedding(latents, ws, "x", **extra)
     else:       # cat([latents, y], dim=1) read in place; batch-1 operands broadcast over the CFG batch
-        x, grid = dit.patch_embedding(latents, ws, "x", y=y, batch=B)
+        x, grid = dit.patch_embedding(latents, ws, "x", y=y, batch=B, **extra)
     S = grid[0] * grid[1] * grid[2]
+    if use_ref:
+        # the reference tokens are frame 0 of a grid one frame longer (wan_video_new.py:1389-1390: concat in
+        # front, RoPE for f + 1 frames): nothing below knows the difference
+        K.ref_rows(ref, x, B, n_ref, S)
+        grid, S = (grid[0] + 1, grid[1], grid[2]), n_ref + S
     img = None
     if clip_feature is not None:
         # context = cat([img_emb(clip_feature), text]) split as CrossAttention.forward does: the first
@@ -295,9 +364,72 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     if sp is not None:
         out = sp.gather_tokens(out, rc)
     T, H2, W2 = grid
+    if use_ref:                                                 # :1464-1465: drop the reference rows
+        lat = torch.empty((B, dit.out_dim, T - 1, 2 * H2, 2 * W2), device=device, dtype=BF16)
+        return K.unpatchify_skip(out, lat, n_ref)
     lat = torch.empty((B, dit.out_dim, T, 2 * H2, 2 * W2), device=device, dtype=BF16)
     K.unpatchify(out, lat)
     return lat
+
+
+def _mine_rows(rows, c, per):
+    """CFG-parallel rank c's sample of per-sample token rows ([2 per, D] -> [per, D]); shared rows pass."""
+    if rows is None or rows.shape[0] == per:
+        return rows
+    return rows[c * per:(c + 1) * per]
+
+
+def _reference_frame(reference_latents, latents, batch):
+    """reference_latents [1 or B, 16, (1,) H, W] as a [Br, 16, H, W] tensor (wan_video_new.py:1386-1387)."""
+    r = reference_latents
+    if r.dim() == 5 and r.shape[2] == 1:
+        r = r[:, :, 0]
+    want = (16,) + tuple(latents.shape[3:])
+    if r.dim() != 4 or tuple(r.shape[1:]) != want or r.shape[0] not in (1, batch):
+        raise ValueError(f"model_fn_wan_video: reference_latents {tuple(reference_latents.shape)}: expected "
+                         f"[1 or {batch}, 16, (1,) {want[1]}, {want[2]}]")
+    return r
+
+
+def _check_camera_input(dit, cc, latents):
+    T, H, W = latents.shape[2:]
+    want = (1, dit.control_adapter.in_dim, T, 8 * H, 8 * W)
+    if tuple(cc.shape) != want:
+        raise ValueError(f"model_fn_wan_video: control_camera_latents_input {tuple(cc.shape)}: expected {want}")
+
+
+def reference_token_rows(dit, reference_latents):
+    """dit.ref_conv's tokens of reference_latents [Br, 16, (1,) H, W] as a tensor of their own
+    [Br (H/2)(W/2), D]: what a denoising loop computes once and hands to every step as
+    model_fn_wan_video(reference_tokens=)."""
+    r = reference_latents[:, :, 0] if reference_latents.dim() == 5 else reference_latents
+    dev = dit.ref_conv.weight.device
+    return dit.ref_tokens(r.to(dev), _workspace(dev)).clone()
+
+
+def camera_token_rows(dit, control_camera_latents_input, batch=1):
+    """dit.control_adapter's output rows [S, D] replicated to [batch S, D]: computed once per call, the
+    residual of every step's patch-embedding GEMM (model_fn_wan_video(camera_tokens=))."""
+    rows = dit.control_adapter(control_camera_latents_input)
+    return rows if batch == 1 else rows.repeat(batch, 1)
+
+
+def fun_control_y(control_latents, y, clip_feature, in_dim, keep_clip=False):
+    """WanVideoUnit_FunControl.process (wan_video_new.py:766-773) -> (y, clip_feature): y = cat([control
+    latents, y_rest]) with y_dim = in_dim - 16 - 16 channels of y_rest -- the last y_dim channels of the
+    image y when both y and clip_feature exist, otherwise zeros, and clip_feature then zeros [1, 257, 1280].
+    keep_clip: clip_feature was given explicitly by the caller and is never replaced."""
+    y_dim = in_dim - control_latents.shape[1] - 16
+    if y_dim < 0:
+        raise ValueError(f"control_video: a DiT with in_dim {in_dim} has no room for 16 control channels")
+    if clip_feature is None or y is None:
+        if not (keep_clip and clip_feature is not None):
+            clip_feature = torch.zeros((1, IMG_TOKENS, 1280), dtype=control_latents.dtype, device=control_latents.device)
+        y = torch.zeros((1, y_dim) + tuple(control_latents.shape[2:]), dtype=control_latents.dtype,
+                        device=control_latents.device)
+    else:
+        y = y[:, -y_dim:]
+    return torch.cat([control_latents, y.to(control_latents.device)], dim=1).contiguous(), clip_feature
 
 
 def image_mask(num_frames, h, w, has_end=False, device=None, dtype=BF16):
@@ -662,8 +794,14 @@ class WanVideoPipeline:
     def denoise(self, latents, context_posi, context_nega, vace_context=None, vace_scale=1.0, cfg_scale=5.0,
                 num_inference_steps=50, sigma_shift=5.0, denoising_strength=1.0, progress_bar_cmd=None,
                 use_graph=None, tea_cache=None, sliding_window_size=None, sliding_window_stride=None,
-                switch_DiT_boundary=0.875, y=None, clip_feature=None, first_frame_latents=None):
+                switch_DiT_boundary=0.875, y=None, clip_feature=None, first_frame_latents=None,
+                reference_latents=None, control_camera_latents_input=None):
         """The loop of wan_video_new.py:515-542 (cfg_merge batched), returns the final latents.
+
+        reference_latents [1, 16, (1,) h, w] / control_camera_latents_input [1, 24, T, H, W] (Wan-Fun
+        control, model_fn_wan_video): neither depends on the step, so each expert's ref_conv tokens and
+        camera adapter rows are computed once, before the loop, and every step -- eager or captured --
+        reads them as constants, like y.
 
         first_frame_latents [1, C, 1, h, w] (a fuse_vae_embedding_in_latents DiT, Wan2.2-TI2V-5B): the
         clean latents of the first frame.  Written into frame 0 of the start latents (:747), every forward
@@ -701,6 +839,7 @@ class WanVideoPipeline:
         window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context,
                                         tea_cache, y=y)
         image_kw = self._image_kwargs(y, clip_feature)
+        self._check_control_modules(reference_latents is not None, control_camera_latents_input is not None)
         ffl = self._first_frame(first_frame_latents, latents)
         if ffl is not None:
             image_kw["fuse_vae_embedding_in_latents"] = True
@@ -726,12 +865,15 @@ class WanVideoPipeline:
             if use_cfg and ctx_cfg is None:
                 ctx_cfg = torch.cat([context_posi, context_nega], 0)
             ctx = ctx_cfg if use_cfg else context_posi
+            control_kw = self._control_kwargs(dit, reference_latents, control_camera_latents_input,
+                                              2 if use_cfg else 1)
 
             def step(t_buf, d_buf):
                 v = self.model_fn(dit=dit, vace=vace, latents=latents, timestep=t_buf, context=ctx,
                                   vace_context=vace_context, vace_scale=vace_scale,
                                   use_unified_sequence_parallel=self.use_unified_sequence_parallel,
-                                  sp_group=self.sp_group, tea_cache=tea_cache, **window_kw, **image_kw)
+                                  sp_group=self.sp_group, tea_cache=tea_cache, **window_kw, **image_kw,
+                                  **control_kw)
                 K.cfg_euler_dev(v[0:1], v[1:2] if use_cfg else None, latents, scale, d_buf)
                 if ffl is not None:
                     latents[:, :, 0:1].copy_(ffl)                                        # :541-542
@@ -775,6 +917,28 @@ class WanVideoPipeline:
             raise ValueError(f"first_frame_latents: expected {want}, got {tuple(first_frame_latents.shape)}")
         return first_frame_latents.to(device=self.device, dtype=BF16).contiguous()
 
+    def _check_control_modules(self, reference, camera):
+        """Every loaded expert has the module the call's Wan-Fun conditioning needs."""
+        for d in (self.dit, self.dit2):
+            if d is None:
+                continue
+            if reference and not getattr(d, "has_ref_conv", False):
+                raise ValueError("reference_image / reference_latents needs a DiT with ref_conv (has_ref_conv); "
+                                 "with two experts, both")
+            if camera and getattr(d, "control_adapter", None) is None:
+                raise ValueError("camera control needs a DiT with control_adapter (add_control_adapter); with two "
+                                 "experts, both")
+
+    def _control_kwargs(self, dit, reference_latents, control_camera_latents_input, batch):
+        """model_fn's Wan-Fun constants of one expert ({} without them): its ref_conv tokens and its camera
+        adapter rows replicated over the step's batch, computed here once."""
+        kw = {}
+        if reference_latents is not None:
+            kw["reference_tokens"] = reference_token_rows(dit, reference_latents.to(self.device))
+        if control_camera_latents_input is not None:
+            kw["camera_tokens"] = camera_token_rows(dit, control_camera_latents_input.to(self.device), batch)
+        return kw
+
     def _image_kwargs(self, y, clip_feature):
         """model_fn's image-conditioning arguments as device bf16 tensors ({} without them)."""
         kw = {}
@@ -805,7 +969,8 @@ class WanVideoPipeline:
                       cfg_scale=1.2, num_inference_steps=4, sigma_shift=2.0, slg_blocks=(), slg_range=(0.2, 0.7),
                       progress_bar_cmd=None, input_latents=None, forward_step=None, skip_backward_step=None,
                       sliding_window_size=None, sliding_window_stride=None, switch_DiT_boundary=0.875,
-                      y=None, clip_feature=None, first_frame_latents=None):
+                      y=None, clip_feature=None, first_frame_latents=None, reference_latents=None,
+                      control_camera_latents_input=None):
         """Config 5's sampler (ditto_comfyui_workflow.json WanVideoSampler 4 / 1.2 / 2.0 / unipc with
         WanVideoSLG): FlowUniPCMultistepScheduler (vstyler.unipc) on fp32 latents, CFG as one
         batch-2 forward, skip-layer guidance on the uncond sample for step fractions in slg_range.
@@ -832,6 +997,8 @@ class WanVideoPipeline:
         window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context,
                                         y=y)
         window_kw.update(self._image_kwargs(y, clip_feature))       # (y / clip_feature: as in denoise)
+        self._check_control_modules(reference_latents is not None, control_camera_latents_input is not None)
+        control_kw = {}     # (expert, batch) -> the Wan-Fun constants, computed at that expert's first step
         from .unipc import FlowUniPCMultistepScheduler, cast
         sched = FlowUniPCMultistepScheduler(shift=1.0)
         sched.set_timesteps(num_inference_steps, shift=sigma_shift)
@@ -870,10 +1037,14 @@ class WanVideoPipeline:
             scale = scales[expert_of[i] - 1]
             use_cfg = scale != 1.0
             ctx = ctx_cfg if use_cfg else context_posi
+            ck = (expert_of[i], use_cfg)
+            if ck not in control_kw:
+                control_kw[ck] = self._control_kwargs(dit, reference_latents, control_camera_latents_input,
+                                                      2 if use_cfg else 1)
             v = self.model_fn(dit=dit, vace=vace, latents=lat16, timestep=t.reshape(1).to(
                 dtype=BF16, device=self.device), context=ctx, vace_context=vace_context, vace_scale=vace_scale,
                 use_unified_sequence_parallel=self.use_unified_sequence_parallel, sp_group=self.sp_group,
-                slg_blocks=slg, **window_kw)
+                slg_blocks=slg, **window_kw, **control_kw[ck])
             v16.zero_()
             K.cfg_euler(v[0:1], v[1:2] if use_cfg else None, v16, scale, 1.0)   # v16 = cfg combine
             cast(v16, v32)
@@ -887,11 +1058,26 @@ class WanVideoPipeline:
                  cfg_scale=5.0, cfg_merge=False, switch_DiT_boundary=0.875, num_inference_steps=50,
                  sigma_shift=5.0, motion_bucket_id=None, tiled=True, tile_size=(30, 52), tile_stride=(15, 26),
                  sliding_window_size=None, sliding_window_stride=None, tea_cache_l1_thresh=None,
-                 tea_cache_model_id="", progress_bar_cmd=None,
+                 tea_cache_model_id="", progress_bar_cmd=None, control_video=None, reference_image=None,
+                 camera_control_direction=None, camera_control_speed=1 / 54,
+                 camera_control_origin=(0, 0.532139961, 0.946026558, 0.5, 0.5, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0),
                  # extensions of this build (the DiT path without T5/VAE):
                  prompt_emb=None, negative_prompt_emb=None, vace_context=None, output_type="video",
-                 input_latents=None, clip_feature=None, first_frame_latents=None, **kwargs):
-        """first_frame_latents [1, C, 1, h, w]: the clean first-frame latents of a
+                 input_latents=None, clip_feature=None, first_frame_latents=None, control_latents=None,
+                 reference_latents=None, control_camera_latents_input=None, **kwargs):
+        """Wan-Fun control (WanVideoUnit_FunControl / FunReference / FunCameraControl, wan_video_new.py:752-845,
+        in the reference's unit order).  control_video (or its precomputed control_latents [1, 16, T', h, w]):
+        VAE-encoded and put in front of y, whose other in_dim - 32 channels are the last ones of the image y
+        when input_image gave both y and CLIP features, else zeros -- clip_feature then defaults to zeros
+        [1, 257, 1280].  reference_image (or reference_latents [1, 16, 1, h, w]) on a has_ref_conv DiT: encoded
+        untiled, its ref_conv tokens lead every forward's sequence; with pipe.image_encoder loaded the CLIP
+        features come from it.  camera_control_direction (with input_image; or a precomputed
+        control_camera_latents_input [1, 24, T', H, W]) on a DiT with control_adapter: the trajectory's Pluecker
+        rays feed the adapter once per call, and y becomes the first frame's latents (in_dim 32) or the
+        mask + latents form (in_dim 36).  A precomputed tensor wins over its image form; an explicit
+        clip_feature= is never replaced.
+
+        first_frame_latents [1, C, 1, h, w]: the clean first-frame latents of a
         fuse_vae_embedding_in_latents DiT (Wan2.2-TI2V-5B image-to-video; denoise).  input_image= on such a
         DiT needs the 48-channel Wan2.2 VAE, which this build does not have.
 
@@ -913,7 +1099,12 @@ class WanVideoPipeline:
                                       "first frame as first_frame_latents=")
         if first_frame_latents is not None and not fused:
             raise ValueError("first_frame_latents needs a DiT with fuse_vae_embedding_in_latents (Wan2.2-TI2V-5B)")
-        self._check_image_args(input_image, end_image, clip_feature)
+        has_control = control_video is not None or control_latents is not None
+        has_reference = reference_image is not None or reference_latents is not None
+        has_camera = camera_control_direction is not None or control_camera_latents_input is not None
+        self._check_control_args(has_control, has_reference, has_camera, input_image)
+        self._check_image_args(input_image, end_image, clip_feature, has_control, reference_image is not None,
+                               has_camera)
         if input_video is not None and input_latents is not None:
             raise ValueError("pass input_video or its precomputed input_latents, not both")
         check_window_args(sliding_window_size, sliding_window_stride)
@@ -950,9 +1141,28 @@ class WanVideoPipeline:
         if input_image is not None:
             y = self.encode_input_image(input_image, end_image, num_frames, height, width, tiled, tile_size, tile_stride)
         # WanVideoUnit_ImageEmbedderCLIP (wan_video_new.py:682-693); an explicit clip_feature= wins
+        explicit_clip = clip_feature is not None
         if clip_feature is None and input_image is not None and self.image_encoder is not None and \
                 self.dit is not None and self.dit.require_clip_embedding:
             clip_feature = self.encode_clip_image(input_image, end_image, height, width)
+        if has_control:                                    # WanVideoUnit_FunControl (:759-773)
+            if control_latents is None:
+                control_latents = self.encode_control_video(control_video, height, width, num_frames, tiled, tile_size,
+                                                            tile_stride)
+            y, clip_feature = fun_control_y(control_latents.to(self.device), y, clip_feature, self._main_dit().in_dim,
+                                            keep_clip=explicit_clip)
+        if has_reference:                                  # WanVideoUnit_FunReference (:784-795)
+            if reference_latents is None:
+                reference_latents = self.encode_reference_image(reference_image, height, width)
+            if reference_image is not None and self.image_encoder is not None and not explicit_clip:
+                clip_feature = self.image_encoder.encode_image(
+                    [self._image_frame(reference_image, "reference_image", height, width)[:, :, 0]]).to(self.torch_dtype)
+        if has_camera:                                     # WanVideoUnit_FunCameraControl (:806-845)
+            if control_camera_latents_input is None:
+                from .camera import control_camera_latents_input as camera_input
+                control_camera_latents_input = camera_input(camera_control_direction, num_frames, height, width,
+                                                            camera_control_speed, camera_control_origin, self.device)
+            y = self.encode_camera_y(input_image, num_frames, height, width, tiled, tile_size, tile_stride, y)
         tea_cache = None
         if tea_cache_l1_thresh is not None:                # WanVideoUnit_TeaCache (:936-947)
             from .teacache import TeaCache
@@ -963,7 +1173,9 @@ class WanVideoPipeline:
                                cfg_scale, num_inference_steps, sigma_shift, denoising_strength, progress_bar_cmd,
                                tea_cache=tea_cache, sliding_window_size=sliding_window_size,
                                sliding_window_stride=sliding_window_stride, switch_DiT_boundary=switch_DiT_boundary,
-                               y=y, clip_feature=clip_feature, first_frame_latents=first_frame_latents)
+                               y=y, clip_feature=clip_feature, first_frame_latents=first_frame_latents,
+                               reference_latents=reference_latents,
+                               control_camera_latents_input=control_camera_latents_input)
         self.last_tea_cache = tea_cache
         if nref:                                            # :545-550
             latents = latents[:, :, nref:].contiguous()
@@ -1035,8 +1247,33 @@ class WanVideoPipeline:
             raise NotImplementedError("T5 text encoder not loaded: pass prompt_emb=/negative_prompt_emb=")
         return self.prompter.encode_prompt(prompt, device=self.device)
 
-    def _check_image_args(self, input_image, end_image, clip_feature):
-        """The image arguments of __call__ against the loaded DiTs, before anything is encoded."""
+    def _main_dit(self):
+        return self.dit if self.dit is not None else self.dit2
+
+    def _check_control_args(self, control, reference, camera, input_image):
+        """The Wan-Fun arguments of __call__ against the loaded DiTs, before anything is encoded."""
+        if not (control or reference or camera):
+            return
+        dits = [d for d in (self.dit, self.dit2) if d is not None]
+        if any(d.fuse_vae_embedding_in_latents for d in dits):
+            raise NotImplementedError("control_video / reference_image / camera control on a "
+                                      "fuse_vae_embedding_in_latents DiT (Wan2.2-TI2V-5B)")
+        if camera and input_image is None:
+            raise ValueError("camera_control_direction needs input_image (the first frame)")
+        for d in dits:
+            if control and (d.in_dim < 32 or not d.require_vae_embedding):
+                raise ValueError(f"control_video needs a Fun-Control DiT whose y holds the 16 control channels "
+                                 f"(in_dim >= 32); the loaded DiT has in_dim {d.in_dim}")
+            if camera and d.in_dim not in (32, 36):
+                raise ValueError(f"camera control gives y 16 or 4 + 16 channels (in_dim 32 or 36); the loaded DiT has "
+                                 f"in_dim {d.in_dim}")
+        self._check_control_modules(reference, camera)
+
+    def _check_image_args(self, input_image, end_image, clip_feature, control=False, reference=False, camera=False):
+        """The image arguments of __call__ against the loaded DiTs, before anything is encoded.  control /
+        reference / camera: the call carries that Wan-Fun conditioning (control_video and camera control
+        assemble y themselves; control_video defaults clip_feature to zeros, a reference image gives its
+        own when an image encoder is loaded)."""
         dits = [d for d in (self.dit, self.dit2) if d is not None]
         if end_image is not None and input_image is None:
             raise ValueError("end_image needs input_image")
@@ -1045,10 +1282,14 @@ class WanVideoPipeline:
                 if d.in_dim <= 16 or not d.require_vae_embedding:
                     raise ValueError(f"input_image needs an image-to-video DiT (in_dim > 16); the loaded DiT has "
                                      f"in_dim {d.in_dim}")
-                if d.in_dim != 36:
+                if d.in_dim != 36 and not (control or camera):
                     raise NotImplementedError(f"input_image gives the 4 + 16 channels of an in_dim 36 DiT; in_dim "
                                               f"{d.in_dim} (Fun-Control) also needs control latents")
         for d in dits:
+            if control:
+                continue                        # FunControl's zero clip_feature when nothing else gave one
+            if reference and self.image_encoder is not None:
+                continue
             if d.has_image_input and d.require_clip_embedding and clip_feature is None and \
                     (input_image is not None or d.in_dim > 16) and \
                     (self.image_encoder is None or input_image is None):
@@ -1096,6 +1337,45 @@ class WanVideoPipeline:
                               tile_stride=tile_stride)
         msk = image_mask(num_frames, height // 8, width // 8, end is not None, device=lat.device, dtype=lat.dtype)
         return torch.cat([msk[None], lat.to(self.torch_dtype)], dim=1).contiguous()
+
+    def encode_control_video(self, control_video, height, width, num_frames, tiled=True, tile_size=(30, 52),
+                             tile_stride=(15, 26)):
+        """WanVideoUnit_FunControl's control_latents (wan_video_new.py:763-765) -> (1, 16, T', h, w) bf16.  As
+        for input_video, the frames must already match the call."""
+        from .vae import frames_to_u8, preprocess_video
+        if self.vae is None:
+            raise RuntimeError("control_video encoding requires a loaded Wan2.1 VAE (or pass control_latents=)")
+        frames = frames_to_u8(control_video, self.device)
+        if tuple(frames.shape) != (num_frames, height, width, 3):
+            raise ValueError(f"control_video must be {num_frames} frames of {height}x{width}, got {tuple(frames.shape)}")
+        return self.vae.encode(preprocess_video(frames), self.device, tiled=tiled, tile_size=tile_size,
+                               tile_stride=tile_stride).to(self.torch_dtype)
+
+    def encode_reference_image(self, reference_image, height, width):
+        """WanVideoUnit_FunReference's reference_latents (wan_video_new.py:788-790) -> (1, 16, 1, h, w): the
+        image resized to (width, height), encoded untiled."""
+        if self.vae is None:
+            raise RuntimeError("reference_image encoding requires a loaded Wan2.1 VAE (or pass reference_latents=)")
+        frame = self._image_frame(reference_image, "reference_image", height, width)
+        return self.vae.encode(frame.to(self.torch_dtype), self.device).to(self.torch_dtype)
+
+    def encode_camera_y(self, input_image, num_frames, height, width, tiled=True, tile_size=(30, 52),
+                        tile_stride=(15, 26), y=None):
+        """WanVideoUnit_FunCameraControl's y (wan_video_new.py:825-844).  in_dim 32: zeros (1, 16, T', h, w)
+        with the untiled encode of the input image in latent frame 0; otherwise the mask + latents form of
+        the image embedder without an end image (the y __call__ already made from input_image, when given)."""
+        dit = self._main_dit()
+        if dit.in_dim - 16 != 16:
+            return y if y is not None else self.encode_input_image(input_image, None, num_frames, height, width, tiled,
+                                                                   tile_size, tile_stride)
+        if self.vae is None:
+            raise RuntimeError("input_image encoding requires a loaded Wan2.1 VAE")
+        frame = self._image_frame(input_image, "input_image", height, width)
+        z = self.vae.encode(frame.to(self.torch_dtype), self.device).to(self.torch_dtype)
+        out = torch.zeros((1, 16, (num_frames - 1) // 4 + 1, height // 8, width // 8), dtype=self.torch_dtype,
+                          device=self.device)
+        out[:, :, :1] = z
+        return out
 
     def encode_input_video(self, input_video, input_latents, height, width, num_frames, tiled, tile_size,
                            tile_stride, vace_reference_image=None):

@@ -1,5 +1,5 @@
 """ctypes binding of libvstyler.so (the C ABI declared in include/vstyler.h, vstyler_image.h,
-vstyler_clip.h, vstyler_seg.h and vstyler_control.h).
+vstyler_clip.h, vstyler_seg.h, vstyler_control.h and vstyler_vae22.h).
 
 The product path has no CPU fallback: if the library is missing every op raises.
 """
@@ -143,6 +143,16 @@ SIGNATURES_CONTROL = {
     "vs_camera_im2col": [_P, _P, _LL, _I, _I, _I, _I, _P],
     "vs_relu": [_P, _LL, _P],
 }
+# the Wan2.2 VAE: wide RMS norm, the Down / Up block shortcuts, pixel (un)patchify (include/vstyler_vae22.h):
+# a sixth table
+SIGNATURES_VAE22 = {
+    "vs_vae22_rmsnorm": [_P, _LL, _P, _LL, _P, _LL, _I, _I, _P],
+    "vs_vae22_avgdown_add": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vs_vae22_dupup_add": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vs_vae22_patchify": [_P, _LL, _P, _I, _I, _I, _P],
+    "vs_vae22_unpatchify": [_P, _LL, _P, _I, _I, _I, _P],
+    "vs_vae22_softmax_split": [_P, _LL, _P, _LL, _LL, _I, _P],
+}
 _RESTYPES = {"vs_strerror": ctypes.c_char_p, "vs_split_workspace_bytes": ctypes.c_longlong,
              "vs_sp_last_error": ctypes.c_char_p}
 
@@ -160,7 +170,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(SIGNATURES_IMAGE.items()) +
                                list(SIGNATURES_CLIP.items()) + list(SIGNATURES_SEG.items()) +
-                               list(SIGNATURES_CONTROL.items())):
+                               list(SIGNATURES_CONTROL.items()) + list(SIGNATURES_VAE22.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, ctypes.c_int)

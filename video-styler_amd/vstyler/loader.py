@@ -277,16 +277,24 @@ def build_vace(state_dict, device, num_layers=None):
 WAN_VAE_HASHES = ("1378ea763357eea97acdef78e65d6d96", "ccc42284ea13e1ad04693284c7a09be6")
 
 
+WAN22_VAE_HASH = "e1de6c02cdac79f8b739f4d3698cd216"   # the Wan2.2 VAE of TI2V-5B (WanVideoVAE38, z_dim 48)
+
+
 def build_vae(state_dict, device):
-    """WanVideoVAE (wan_video_vae.py:1058) from the civitai layout (optionally under 'model_state')."""
+    """WanVideoVAE (wan_video_vae.py:1058), or WanVideoVAE38 (:1354) for the Wan2.2 layout (its hash, or a
+    48-row conv2), from the civitai layout (optionally under 'model_state')."""
     sd = state_dict.get("model_state", state_dict)
-    if hash_state_dict_keys(sd) not in WAN_VAE_HASHES and \
+    h = hash_state_dict_keys(sd)
+    if h not in WAN_VAE_HASHES + (WAN22_VAE_HASH,) and \
             not ("encoder.conv1.weight" in sd and "decoder.head.2.weight" in sd and "conv2.weight" in sd):
         return None
-    from .vae import WanVideoVAE
+    from .vae import WanVideoVAE, WanVideoVAE38
     z_dim = sd["conv2.weight"].shape[0]
+    if h == WAN22_VAE_HASH or z_dim == 48:
+        return WanVideoVAE38(z_dim=z_dim, dim=sd["encoder.conv1.weight"].shape[0],
+                             dec_dim=sd["decoder.head.2.weight"].shape[1], device=device).load_state_dict(sd)
     if z_dim != 16:
-        return None  # the 48-channel Wan2.2 VAE (WanVideoVAE38) is out of scope
+        return None
     return WanVideoVAE(z_dim=z_dim, dim=sd["encoder.conv1.weight"].shape[0], device=device).load_state_dict(sd)
 
 

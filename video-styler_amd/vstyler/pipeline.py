@@ -1079,7 +1079,10 @@ class WanVideoPipeline:
 
         first_frame_latents [1, C, 1, h, w]: the clean first-frame latents of a
         fuse_vae_embedding_in_latents DiT (Wan2.2-TI2V-5B image-to-video; denoise).  input_image= on such a
-        DiT needs the 48-channel Wan2.2 VAE, which this build does not have.
+        DiT (WanVideoUnit_ImageEmbedderFused, wan_video_new.py:731-748) is resized, encoded by the 48-channel
+        Wan2.2 VAE (WanVideoVAE38 as pipe.vae) and passed on as first_frame_latents; an explicit
+        first_frame_latents= wins, and without that VAE the call raises NotImplementedError.  input_video /
+        input_latents and output_type="video" go through the same VAE at its geometry (48 channels, stride 16).
 
         wan_video_new.py:416-560 for the Ditto path (T2V/VACE/video-to-video) and image-to-video (no
         audio/camera inputs).  input_image (and end_image) on a DiT with in_dim > 16 become y
@@ -1093,10 +1096,15 @@ class WanVideoPipeline:
         if motion_bucket_id is not None:
             raise NotImplementedError("motion_bucket_id is outside the Ditto hot path of this build")
         fused = self.dit is not None and self.dit.fuse_vae_embedding_in_latents
+        fused_image = None                                  # WanVideoUnit_ImageEmbedderFused's image (below)
         if input_image is not None and fused:
-            raise NotImplementedError("input_image on a fuse_vae_embedding_in_latents DiT (Wan2.2-TI2V-5B) needs the "
-                                      "48-channel Wan2.2 VAE, which this build does not have: pass the encoded "
-                                      "first frame as first_frame_latents=")
+            if first_frame_latents is None:
+                if self.vae is None or self.vae.z_dim != 48:
+                    raise NotImplementedError("input_image on a fuse_vae_embedding_in_latents DiT (Wan2.2-TI2V-5B) "
+                                              "needs the 48-channel Wan2.2 VAE (WanVideoVAE38) loaded as pipe.vae: "
+                                              "load it, or pass the encoded first frame as first_frame_latents=")
+                fused_image = input_image
+            input_image = None                              # no y / CLIP branch on such a DiT
         if first_frame_latents is not None and not fused:
             raise ValueError("first_frame_latents needs a DiT with fuse_vae_embedding_in_latents (Wan2.2-TI2V-5B)")
         has_control = control_video is not None or control_latents is not None
@@ -1115,6 +1123,8 @@ class WanVideoPipeline:
         height, width, num_frames = self.check_resize_height_width(height, width, num_frames, output_type)
         T = (num_frames - 1) // 4 + 1
         zc, zs = self.latent_geometry(output_type)
+        if fused_image is not None:                         # wan_video_new.py:741-748
+            first_frame_latents = self.encode_first_frame(fused_image, height, width, tiled, tile_size, tile_stride)
         # WanVideoUnit_NoiseInitializer (wan_video_new.py:578-587): f reference images add f latent
         # frames, and the noise is rolled so the last f frames come first
         nref = 0
@@ -1182,7 +1192,7 @@ class WanVideoPipeline:
         if output_type == "latents":
             return latents
         if self.vae is None:
-            raise RuntimeError("VAE decode requires a loaded Wan2.1 VAE (or use output_type='latents')")
+            raise RuntimeError("VAE decode requires a loaded VAE (or use output_type='latents')")
         video = self.vae.decode(latents, device=self.device, tiled=tiled, tile_size=tile_size, tile_stride=tile_stride)
         return self.vae_output_to_video(video, output_type)
 
@@ -1310,6 +1320,14 @@ class WanVideoPipeline:
             raise ValueError(f"{name} must be one {height}x{width} RGB image, got {tuple(u8.shape)}")
         return preprocess_video(u8)
 
+    def encode_first_frame(self, input_image, height, width, tiled=True, tile_size=(30, 52), tile_stride=(15, 26)):
+        """WanVideoUnit_ImageEmbedderFused (wan_video_new.py:741-748) -> first_frame_latents (1, 48, 1, h, w)
+        bf16: the image as _image_frame makes it, encoded as a one-frame video by the Wan2.2 VAE."""
+        image = self._image_frame(input_image, "input_image", height, width)
+        z = self.vae.encode([image[0].to(self.torch_dtype)], self.device, tiled=tiled, tile_size=tile_size,
+                            tile_stride=tile_stride)
+        return z.to(self.torch_dtype)
+
     def encode_clip_image(self, input_image, end_image, height, width):
         """WanVideoUnit_ImageEmbedderCLIP (wan_video_new.py:675-693) -> clip_feature (1, 257, 1280) bf16:
         image_encoder.encode_image of the frame encode_input_image builds; end_image's features follow
@@ -1381,11 +1399,13 @@ class WanVideoPipeline:
                            tile_stride, vace_reference_image=None):
         """WanVideoUnit_InputVideoEmbedder (wan_video_new.py:598-609): preprocess + VAE-encode the
         video (or take its precomputed latents), with the latent of the one reference image, encoded
-        untiled, in front along time -> (1, 16, f + T', h, w) bf16.  The reference neither truncates
+        untiled, in front along time -> (1, 16, f + T', h, w) bf16 (48 channels at stride 16 with the Wan2.2
+        VAE or a DiT of such latents: latent_geometry).  The reference neither truncates
         nor resizes the video here, so a video that does not match the call is an error."""
         from .vae import frames_to_u8, preprocess_video
         t_lat = (num_frames - 1) // 4 + 1
-        want = (1, 16, t_lat, height // 8, width // 8)
+        zc, zs = self.latent_geometry(None if input_video is not None else "latents")   # input_latents: the DiT's
+        want = (1, zc, t_lat, height // zs, width // zs)
         refs = None
         if vace_reference_image is not None:
             refs = vace_reference_image              # a list of images, (f, H, W, 3) uint8, or one image
@@ -1405,7 +1425,7 @@ class WanVideoPipeline:
         elif tuple(input_latents.shape) != want:
             raise ValueError(f"input_latents must be {want}, got {tuple(input_latents.shape)}")
         if self.vae is None and (input_video is not None or refs is not None):
-            raise RuntimeError("input_video encoding requires a loaded Wan2.1 VAE (or pass input_latents=)")
+            raise RuntimeError("input_video encoding requires a loaded VAE (or pass input_latents=)")
         if input_video is not None:
             input_latents = self.vae.encode(preprocess_video(frames), self.device, tiled=tiled, tile_size=tile_size,
                                             tile_stride=tile_stride)

@@ -1,4 +1,5 @@
-"""Wan2.1 causal 3-D VAE on gfx950 (replaces diffsynth/models/wan_video_vae.py, Wan2.1 part).
+"""The Wan causal 3-D VAEs on gfx950 (replaces diffsynth/models/wan_video_vae.py): the Wan2.1 16-channel
+stride-8 `WanVideoVAE` and, at the end of the file, the Wan2.2 48-channel stride-16 `WanVideoVAE38`.
 
 Drop-in surface: `WanVideoVAE.encode(videos, device, tiled, tile_size, tile_stride)` and
 `.decode(hidden_states, device, tiled, tile_size, tile_stride)` (wan_video_vae.py:1218-1247), same
@@ -20,6 +21,7 @@ Execution is MI355X-first, not a translation of the reference's chunk loop:
   1x1 convs of VideoVAE_ are the same kernel.  Tiles never leave HBM (the reference moves each
   tile host<->device, :1125-1126,1177-1178); blending follows the reference's bf16 task order.
 """
+import functools
 import math
 
 import torch
@@ -34,6 +36,19 @@ VAE_MEAN = [-0.7571, -0.7089, -0.9113, 0.1075, -0.1745, 0.9653, -0.1517, 1.5508,
             0.4134, -0.0715, 0.5517, -0.3632, -0.1922, -0.9497, 0.2503, -0.2921]
 VAE_STD = [2.8184, 1.4541, 2.3275, 2.6558, 1.2196, 1.7708, 2.6052, 2.0743,
            3.2687, 2.1526, 2.8652, 1.5579, 1.6382, 1.1253, 2.8251, 1.9160]
+# wan_video_vae.py:1359-1374 (WanVideoVAE38)
+VAE38_MEAN = [-0.2289, -0.0052, -0.1323, -0.2339, -0.2799, 0.0174, 0.1838, 0.1557,
+              -0.1382, 0.0542, 0.2813, 0.0891, 0.1570, -0.0098, 0.0375, -0.1825,
+              -0.2246, -0.1207, -0.0698, 0.5109, 0.2665, -0.2108, -0.2158, 0.2502,
+              -0.2055, -0.0322, 0.1109, 0.1567, -0.0729, 0.0899, -0.2799, -0.1230,
+              -0.0313, -0.1649, 0.0117, 0.0723, -0.2839, -0.2083, -0.0520, 0.3748,
+              0.0152, 0.1957, 0.1433, -0.2944, 0.3573, -0.0548, -0.1681, -0.0667]
+VAE38_STD = [0.4765, 1.0364, 0.4514, 1.1677, 0.5313, 0.4990, 0.4818, 0.5013,
+             0.8158, 1.0344, 0.5894, 1.0901, 0.6885, 0.6165, 0.8454, 0.4978,
+             0.5759, 0.3523, 0.7135, 0.6804, 0.5833, 1.4146, 0.8986, 0.5659,
+             0.7069, 0.5338, 0.4889, 0.4917, 0.4069, 0.4999, 0.6866, 0.4093,
+             0.5709, 0.6065, 0.6415, 0.4944, 0.5726, 1.2042, 0.5458, 1.6887,
+             0.3971, 1.0600, 0.3943, 0.5537, 0.5444, 0.4089, 0.7468, 0.7744]
 
 
 def _r32(c):
@@ -118,11 +133,12 @@ def batched_gemm(a, a_zs, lda, rows, k, b, b_zs, ldb, n_out, y, y_zs, ldy, nz, o
 
 
 def rmsnorm(x, gamma, silu, out=None):
-    """RMS_norm (+SiLU) over the channel dim of a channels-last tensor (in place if out is x)."""
+    """RMS_norm (+SiLU) over the channel dim of a channels-last tensor (in place if out is x): rows up to
+    384 wide through vs_vae_rmsnorm, wider ones (the Wan2.2 VAE's 416-1024) through vs_vae22_rmsnorm."""
     c = x.shape[-1]
     out = torch.empty_like(x) if out is None else out
-    _lib.check(_lib.load().vs_vae_rmsnorm(x.data_ptr(), c, out.data_ptr(), c, gamma.data_ptr(),
-                                          x.numel() // c, c, int(silu), _stream(x)))
+    fn = _lib.load().vs_vae_rmsnorm if c <= 384 else _lib.load().vs_vae22_rmsnorm
+    _lib.check(fn(x.data_ptr(), c, out.data_ptr(), c, gamma.data_ptr(), x.numel() // c, c, int(silu), _stream(x)))
     return out
 
 
@@ -132,10 +148,36 @@ def copy_first_frame(src, dst):
                                               n, h * w * c, _stream(src)))
 
 
+def _res_shapes(d, p, i, o):
+    d[p + "residual.0.gamma"] = (i, 1, 1, 1)
+    d[p + "residual.2.weight"], d[p + "residual.2.bias"] = (o, i, 3, 3, 3), (o,)
+    d[p + "residual.3.gamma"] = (o, 1, 1, 1)
+    d[p + "residual.6.weight"], d[p + "residual.6.bias"] = (o, o, 3, 3, 3), (o,)
+    if i != o:
+        d[p + "shortcut.weight"], d[p + "shortcut.bias"] = (o, i, 1, 1, 1), (o,)
+
+
+def _attn_shapes(d, p, c):
+    d[p + "norm.gamma"] = (c, 1, 1)
+    d[p + "to_qkv.weight"], d[p + "to_qkv.bias"] = (3 * c, c, 1, 1), (3 * c,)
+    d[p + "proj.weight"], d[p + "proj.bias"] = (c, c, 1, 1), (c,)
+
+
+def _resample_shapes(d, p, c, mode, keep_width=False):
+    """Resample (:82-118); keep_width: Resample38 (:227-265), whose upsample conv is dim -> dim."""
+    co = c // 2 if mode.startswith("up") and not keep_width else c
+    d[p + "resample.1.weight"], d[p + "resample.1.bias"] = (co, c, 3, 3), (co,)
+    if mode.endswith("3d"):
+        ct = 2 * c if mode == "upsample3d" else c
+        d[p + "time_conv.weight"], d[p + "time_conv.bias"] = (ct, c, 3, 1, 1), (ct,)
+
+
 class WanVideoVAE:
     """Replaces WanVideoVAE (wan_video_vae.py:1058-1252) for the Wan2.1 16-channel VAE."""
 
     upsampling_factor = 8
+    MEAN, STD = VAE_MEAN, VAE_STD
+    pixel_cpad = 32          # channels of the gathered pixel tiles (RGB first, the rest zero)
 
     def __init__(self, z_dim=16, dim=96, dim_mult=(1, 2, 4, 4), num_res_blocks=2,
                  temperal_downsample=(False, True, True), device="cuda", attn_bytes=2 << 30,
@@ -145,8 +187,8 @@ class WanVideoVAE:
         self.device = torch.device(device)
         self.attn_bytes = attn_bytes
         self.max_tile_batch = max_tile_batch
-        self.mean = torch.tensor(VAE_MEAN[:z_dim]).to(BF16).to(self.device)
-        self.inv_std = (1.0 / torch.tensor(VAE_STD[:z_dim])).to(BF16).to(self.device)
+        self.mean = torch.tensor(self.MEAN[:z_dim]).to(BF16).to(self.device)
+        self.inv_std = (1.0 / torch.tensor(self.STD[:z_dim])).to(BF16).to(self.device)
         self.params = {}
         self.cw = {}
         self.enc_layers, self.enc_dims = self._encoder_layers()
@@ -203,26 +245,7 @@ class WanVideoVAE:
     def state_dict_shapes(self):
         """The civitai file layout of this configuration (keys without 'model.')."""
         d, z = {}, self.z_dim
-
-        def res(p, i, o):
-            d[p + "residual.0.gamma"] = (i, 1, 1, 1)
-            d[p + "residual.2.weight"], d[p + "residual.2.bias"] = (o, i, 3, 3, 3), (o,)
-            d[p + "residual.3.gamma"] = (o, 1, 1, 1)
-            d[p + "residual.6.weight"], d[p + "residual.6.bias"] = (o, o, 3, 3, 3), (o,)
-            if i != o:
-                d[p + "shortcut.weight"], d[p + "shortcut.bias"] = (o, i, 1, 1, 1), (o,)
-
-        def attn(p, c):
-            d[p + "norm.gamma"] = (c, 1, 1)
-            d[p + "to_qkv.weight"], d[p + "to_qkv.bias"] = (3 * c, c, 1, 1), (3 * c,)
-            d[p + "proj.weight"], d[p + "proj.bias"] = (c, c, 1, 1), (c,)
-
-        def resample(p, c, mode):
-            co = c // 2 if mode.startswith("up") else c
-            d[p + "resample.1.weight"], d[p + "resample.1.bias"] = (co, c, 3, 3), (co,)
-            if mode.endswith("3d"):
-                ct = 2 * c if mode == "upsample3d" else c
-                d[p + "time_conv.weight"], d[p + "time_conv.bias"] = (ct, c, 3, 1, 1), (ct,)
+        res, attn, resample = (functools.partial(f, d) for f in (_res_shapes, _attn_shapes, _resample_shapes))
 
         strip = lambda p: p[len("model."):]  # noqa: E731
         e0, top = self.enc_dims[0], self.enc_dims[-1]
@@ -393,6 +416,10 @@ class WanVideoVAE:
                 tasks.append((h, h + size[0], w, w + size[1]))
         return tasks
 
+    def _tile_batch(self, t, th, tw, decode):
+        """Tiles of (t, th, tw) source frames per batch."""
+        return self.max_tile_batch
+
     def _run_tasks(self, src, tasks, H, W, t_src, t_use, cpad, gather_mode, fn):
         """Gather every task's tile (batched per tile shape) and run fn on the batches.
         Returns {task index: (batch output, row)}."""
@@ -406,8 +433,9 @@ class WanVideoVAE:
         a = self.mean.data_ptr() if gather_mode else None
         b = self.inv_std.data_ptr() if gather_mode else None
         for (th, tw), idx in groups.items():
-            for g0 in range(0, len(idx), self.max_tile_batch):
-                ids = idx[g0:g0 + self.max_tile_batch]
+            nb = self._tile_batch(t_use, th, tw, gather_mode == 2)
+            for g0 in range(0, len(idx), nb):
+                ids = idx[g0:g0 + nb]
                 x = torch.empty((len(ids), t_use, th, tw, cpad), dtype=BF16, device=src.device)
                 for j, i in enumerate(ids):
                     h, _, w, _ = tasks[i]
@@ -458,7 +486,7 @@ class WanVideoVAE:
             tasks = self.tile_tasks(H, W, size, stride)
         else:  # single_encode == one all-bound tile (mask 1, weight 1: bit-identical)
             size, stride, tasks = (H, W), (H, W), [(0, H, 0, W)]
-        outs = self._run_tasks(video, tasks, H, W, T, 1 + 4 * (t_lat - 1), 32, 0, self.encode_tiles)
+        outs = self._run_tasks(video, tasks, H, W, T, 1 + 4 * (t_lat - 1), self.pixel_cpad, 0, self.encode_tiles)
         return self._blend(tasks, outs, H, W, 0, size, stride, self.z_dim, t_lat, 2 * self.z_dim, False, 1, f)
 
     def _decode_one(self, z, tiled, tile_size, tile_stride):
@@ -487,6 +515,212 @@ class WanVideoVAE:
 
     def decode(self, hidden_states, device=None, tiled=False, tile_size=(34, 34), tile_stride=(18, 16)):
         return torch.stack([self._decode_one(z, tiled, tile_size, tile_stride) for z in hidden_states])
+
+
+def avgdown_add(x, y, ft, fs):
+    """y += AvgDown3D(x) (vs_vae22_avgdown_add), in place; x, y contiguous channels-last."""
+    n, t, h, w, c = x.shape
+    t_out = 1 + (t - 1) // 2 if ft == 2 else t
+    if tuple(y.shape[:4]) != (n, t_out, h // fs, w // fs) or not (x.is_contiguous() and y.is_contiguous()):
+        raise ValueError(f"avgdown_add: {tuple(x.shape)} -> {tuple(y.shape)} with factors ({ft}, {fs})")
+    _lib.check(_lib.load().vs_vae22_avgdown_add(x.data_ptr(), y.data_ptr(), n, t, h, w, c, y.shape[-1], ft, fs,
+                                                _stream(x)))
+    return y
+
+
+def dupup_add(x, y, ft, fs):
+    """y += DupUp3D(x) with the first frame's first_chunk rule (vs_vae22_dupup_add), in place."""
+    n, t, h, w, c = x.shape
+    if tuple(y.shape[:4]) != (n, ft * (t - 1) + 1, fs * h, fs * w) or not (x.is_contiguous() and y.is_contiguous()):
+        raise ValueError(f"dupup_add: {tuple(x.shape)} -> {tuple(y.shape)} with factors ({ft}, {fs})")
+    _lib.check(_lib.load().vs_vae22_dupup_add(x.data_ptr(), y.data_ptr(), n, t, h, w, c, y.shape[-1], ft, fs,
+                                              _stream(x)))
+    return y
+
+
+def patchify2(x):
+    """[n, t, h, w, >= 4] RGB-first pixels -> [n, t, h / 2, w / 2, 32] (vs_vae22_patchify)."""
+    n, t, h, w, c = x.shape
+    y = torch.empty((n, t, h // 2, w // 2, 32), dtype=BF16, device=x.device)
+    _lib.check(_lib.load().vs_vae22_patchify(x.data_ptr(), c, y.data_ptr(), n * t, h, w, _stream(x)))
+    return y
+
+
+def unpatchify2(x):
+    """[n, t, h, w, >= 12] -> [n, t, 2 h, 2 w, 4] RGB0 pixels (vs_vae22_unpatchify)."""
+    n, t, h, w, c = x.shape
+    y = torch.empty((n, t, 2 * h, 2 * w, 4), dtype=BF16, device=x.device)
+    _lib.check(_lib.load().vs_vae22_unpatchify(x.data_ptr(), c, y.data_ptr(), n * t, h, w, _stream(x)))
+    return y
+
+
+class WanVideoVAE38(WanVideoVAE):
+    """Replaces WanVideoVAE38 (wan_video_vae.py:1354-1382: VideoVAE38_ :1269-1351 over Encoder3d_38 :620-733
+    and Decoder3d_38 :842-940), the Wan2.2 VAE of TI2V-5B: 48 latent channels at stride 16.
+
+    Pixels are 2x2-patchified to 12 channels; the encoder (dim 160) and the decoder (dec_dim 256) are
+    four Down_ / Up_ResidualBlocks (:442-514) whose main path is the Wan2.1 layers -- ResidualBlocks and
+    a Resample38 that keeps its width (:227-265) -- and whose shortcut is parameter-free: AvgDown3D
+    (:345-395) / DupUp3D (:398-439) of the block's input, added in place by one kernel each.  In the
+    whole-sequence form the shortcuts pair frames as the main path does: a temporal AvgDown3D averages
+    frames (2j-1, 2j) with a zero frame -1, a temporal DupUp3D's first_chunk rule drops the first copy of
+    latent frame 0.  Tiling, blending, normalisation and the encode-list quirk are WanVideoVAE's at
+    factor 16; a batch of tiles is sized by bytes (tile_bytes: a sizing target, not a cap), since one
+    480 x 832 tile of 121 frames is 6.2 GB per 256-channel activation -- measured at 1280x704x121: decode
+    peaks at 71 GiB with 3 tiles per batch, encode at 32 GiB with 4."""
+
+    upsampling_factor = 16
+    MEAN, STD = VAE38_MEAN, VAE38_STD
+    pixel_cpad = 4
+
+    def __init__(self, z_dim=48, dim=160, dec_dim=256, dim_mult=(1, 2, 4, 4), num_res_blocks=2,
+                 temperal_downsample=(False, True, True), device="cuda", attn_bytes=2 << 30, max_tile_batch=16,
+                 tile_bytes=64 << 30):
+        self.dec_dim = dec_dim
+        self.tile_bytes = tile_bytes
+        super().__init__(z_dim, dim, dim_mult, num_res_blocks, temperal_downsample, device, attn_bytes,
+                         max_tile_batch)
+
+    # ---------------------------------------------------------------- structure (:638-662, :861-882)
+    def _blocks(self, part, dims, flags, nres, sub):
+        """[(layers of the main path, (c_in, c_out, ft, fs) of the shortcut or None)] per block; flags: the
+        temporal flags of the first len(flags) blocks (:648-650, :874)."""
+        last = len(self.dim_mult) - 1
+        out = []
+        for i, (a, b) in enumerate(zip(dims[:-1], dims[1:])):
+            p = f"model.{part}.{sub}.{i}.{sub}."
+            temporal = i < len(flags) and flags[i]
+            layers = [("res", f"{p}{k}.", (a if k == 0 else b, b)) for k in range(nres)]
+            if i != last:
+                mode = ("down" if part == "encoder" else "up") + "sample" + ("3d" if temporal else "2d")
+                layers.append(("resample", f"{p}{nres}.", (b, mode)))
+            ft, fs = 2 if temporal else 1, 2 if i != last else 1
+            out.append((layers, (a, b, ft, fs) if part == "encoder" or i != last else None))
+        return out
+
+    def _encoder_layers(self):
+        dims = [self.dim * u for u in (1,) + self.dim_mult]
+        return self._blocks("encoder", dims, self.temperal_downsample, self.nrb, "downsamples"), dims
+
+    def _decoder_layers(self):
+        dims = [self.dec_dim * u for u in (self.dim_mult[-1],) + self.dim_mult[::-1]]
+        return self._blocks("decoder", dims, self.temperal_downsample[::-1], self.nrb + 1, "upsamples"), dims
+
+    def state_dict_shapes(self):
+        """The civitai file layout of this configuration (keys without 'model.'); the real one has 196
+        tensors and hashes (with shapes) to the registry's e1de6c02cdac79f8b739f4d3698cd216."""
+        d, z = {}, self.z_dim
+        res, attn = functools.partial(_res_shapes, d), functools.partial(_attn_shapes, d)
+
+        def blocks(bl):
+            for layers, _ in bl:
+                for kind, p, args in layers:
+                    p = p[len("model."):]
+                    res(p, *args) if kind == "res" else _resample_shapes(d, p, *args, keep_width=True)
+
+        e0, top = self.enc_dims[0], self.enc_dims[-1]
+        d["encoder.conv1.weight"], d["encoder.conv1.bias"] = (e0, 12, 3, 3, 3), (e0,)
+        blocks(self.enc_layers)
+        res("encoder.middle.0.", top, top)
+        attn("encoder.middle.1.", top)
+        res("encoder.middle.2.", top, top)
+        d["encoder.head.0.gamma"] = (top, 1, 1, 1)
+        d["encoder.head.2.weight"], d["encoder.head.2.bias"] = (2 * z, top, 3, 3, 3), (2 * z,)
+        d["conv1.weight"], d["conv1.bias"] = (2 * z, 2 * z, 1, 1, 1), (2 * z,)
+        d["conv2.weight"], d["conv2.bias"] = (z, z, 1, 1, 1), (z,)
+        d0, dl = self.dec_dims[0], self.dec_dims[-1]
+        d["decoder.conv1.weight"], d["decoder.conv1.bias"] = (d0, z, 3, 3, 3), (d0,)
+        res("decoder.middle.0.", d0, d0)
+        attn("decoder.middle.1.", d0)
+        res("decoder.middle.2.", d0, d0)
+        blocks(self.dec_layers)
+        d["decoder.head.0.gamma"] = (dl, 1, 1, 1)
+        d["decoder.head.2.weight"], d["decoder.head.2.bias"] = (12, dl, 3, 3, 3), (12,)
+        return d
+
+    # ---------------------------------------------------------------- layers
+    def _run_blocks(self, x, blocks, shortcut_add):
+        for layers, sc in blocks:
+            y = self._run_layers(x, layers)
+            if sc is not None:
+                shortcut_add(x, y, sc[2], sc[3])
+            x = y
+        return x
+
+    def _attn_block(self, x, p, flash=None):
+        """AttentionBlock on the GEMM route at every width, with the probabilities kept as a bf16 hi / lo pair
+        (vs_vae22_softmax_split): P.V is one GEMM over K = 2 hwp, [hi | lo] against V^T laid out twice, so P
+        enters the fp32 sum to about 16 bits.  WanVideoVAE's routes round P to bf16; in this model the
+        decoder's DupUp3D shortcuts carry the middle block's output unattenuated to every level, and that
+        rounding alone moved the tiny model's decode by 1.4 % rel-L2.  The block is below 0.1 % of a decode."""
+        n, t, h, w, c = x.shape
+        hw, nz = h * w, n * t
+        xn = rmsnorm(x, self.params[p + "norm.gamma"], silu=False)
+        qkv = self._conv1(xn, p + "to_qkv.")                      # [n, t, h, w, 3c]
+        del xn
+        o = torch.empty((n, t, h, w, c), dtype=BF16, device=x.device)
+        hwp = _r32(hw)
+        zc = max(1, min(nz, self.attn_bytes // (hw * hwp * 4)))
+        s = torch.empty((zc, hw, hwp), dtype=torch.float32, device=x.device)
+        pm = torch.empty((zc, hw, 2 * hwp), dtype=BF16, device=x.device)
+        vt = torch.empty((zc, c, 2 * hwp), dtype=BF16, device=x.device)
+        lib = _lib.load()
+        st = _stream(x)
+        q_all = qkv.view(nz, hw, 3 * c)
+        o_all = o.view(nz, hw, c)
+        for z0 in range(0, nz, zc):
+            zn = min(zc, nz - z0)
+            q = q_all[z0]
+            batched_gemm(q, hw * 3 * c, 3 * c, hw, c, q[:, c:], hw * 3 * c, 3 * c, hw, s, hw * hwp, hwp, zn,
+                         out_f32=True, alpha=1.0 / math.sqrt(c))
+            _lib.check(lib.vs_vae22_softmax_split(s.data_ptr(), hwp, pm.data_ptr(), 2 * hwp, zn * hw, hw, st))
+            # V^T into the first half of every row (the transpose zero-fills the rest), then copied to the second
+            _lib.check(lib.vs_vae_transpose(q[:, 2 * c:].data_ptr(), hw * 3 * c, 3 * c, vt.data_ptr(), c * 2 * hwp,
+                                            2 * hwp, zn, hw, c, st))
+            _lib.check(lib.vs_vae_copy_frames(vt.data_ptr(), 2 * hwp, vt[0, 0, hwp:].data_ptr(), 2 * hwp, zn * c, hwp,
+                                              st))
+            batched_gemm(pm, hw * 2 * hwp, 2 * hwp, hw, 2 * hwp, vt, c * 2 * hwp, 2 * hwp, c, o_all[z0], hw * c, c, zn)
+        del s, pm, vt, qkv
+        return conv(o, self.cw[p + "proj."], (t, h, w), res=x)
+
+    def encode_tiles(self, x):
+        """patchify + Encoder3d_38 + VideoVAE38_.conv1 on a batch of pixel tiles x [n, T, H, W, >= 4] (RGB in
+        channels 0-2, T = 1 + 4k).  Returns [n, 1 + k, H/16, W/16, 2*z_dim]; mu = channels [0, z_dim)."""
+        x = self._conv3(patchify2(x), "model.encoder.conv1.")
+        x = self._run_blocks(x, self.enc_layers, avgdown_add)
+        x = self._res_block(x, "model.encoder.middle.0.")
+        x = self._attn_block(x, "model.encoder.middle.1.")
+        x = self._res_block(x, "model.encoder.middle.2.")
+        x = rmsnorm(x, self.params["model.encoder.head.0.gamma"], silu=True, out=x)
+        x = self._conv3(x, "model.encoder.head.2.")
+        return self._conv1(x, "model.conv1.")
+
+    def decode_tiles(self, z):
+        """VideoVAE38_.conv2 + Decoder3d_38 + unpatchify on de-normalised latent tiles z [n, T, h, w, 64]
+        (channels >= z_dim zero).  Returns [n, 4T-3, 16h, 16w, 4] (RGB in channels 0-2)."""
+        n, t, h, w, _ = z.shape
+        x = torch.zeros((n, t, h, w, _r32(self.z_dim)), dtype=BF16, device=z.device)
+        self._conv1(z, "model.conv2.", y=x)
+        x = self._conv3(x, "model.decoder.conv1.")
+        x = self._res_block(x, "model.decoder.middle.0.")
+        x = self._attn_block(x, "model.decoder.middle.1.")
+        x = self._res_block(x, "model.decoder.middle.2.")
+        x = self._run_blocks(x, self.dec_layers, dupup_add)
+        x = rmsnorm(x, self.params["model.decoder.head.0.gamma"], silu=True, out=x)
+        n, t, h, w, _ = x.shape
+        y = torch.empty((n, t, h, w, 16), dtype=BF16, device=x.device)   # 12 channels, rows 32 B apart
+        return unpatchify2(conv(x, self.cw["model.decoder.head.2."], (t, h, w), pad=(2, 1, 1), y=y))
+
+    def _tile_batch(self, t, th, tw, decode):
+        """Tiles per batch so that the live activations at the widest level (half the pixel resolution,
+        dim or dec_dim channels) stay within tile_bytes: a residual block holds three (its input, the
+        normed / convolved intermediate, its output), the encoder's first Down block a fourth (the block
+        input its shortcut averages); the decoder's last block has no shortcut."""
+        if decode:
+            live = 3 * (4 * t - 3) * (8 * th) * (8 * tw) * self.dec_dims[-1] * 2
+        else:
+            live = 4 * t * (th // 2) * (tw // 2) * self.enc_dims[0] * 2
+        return max(1, min(self.max_tile_batch, self.tile_bytes // live))
 
 
 def vae_output_to_u8(video):

@@ -1,5 +1,5 @@
 """ctypes binding of libvstyler.so (the C ABI declared in include/vstyler.h, vstyler_image.h,
-vstyler_clip.h, vstyler_seg.h, vstyler_control.h and vstyler_vae22.h).
+vstyler_clip.h, vstyler_seg.h, vstyler_control.h, vstyler_vae22.h and vstyler_animate.h).
 
 The product path has no CPU fallback: if the library is missing every op raises.
 """
@@ -153,6 +153,13 @@ SIGNATURES_VAE22 = {
     "vs_vae22_unpatchify": [_P, _LL, _P, _I, _I, _I, _P],
     "vs_vae22_softmax_split": [_P, _LL, _P, _LL, _LL, _I, _P],
 }
+# Wan2.2-Animate: the face adapter's attention, the per-head RMSNorm, LayerNorm -> SiLU
+# (include/vstyler_animate.h): a seventh table
+SIGNATURES_ANIMATE = {
+    "vs_face_attn": [_P, _LL, _P, _P, _LL, _LL, _P, _LL, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P],
+    "vs_head_rmsnorm": [_P, _LL, _I, _I, _I, _P, _F, _P],
+    "vs_ln_silu": [_P, _LL, _P, _LL, _I, _I, _I, _F, _P],
+}
 _RESTYPES = {"vs_strerror": ctypes.c_char_p, "vs_split_workspace_bytes": ctypes.c_longlong,
              "vs_sp_last_error": ctypes.c_char_p}
 
@@ -170,7 +177,8 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(SIGNATURES_IMAGE.items()) +
                                list(SIGNATURES_CLIP.items()) + list(SIGNATURES_SEG.items()) +
-                               list(SIGNATURES_CONTROL.items()) + list(SIGNATURES_VAE22.items())):
+                               list(SIGNATURES_CONTROL.items()) + list(SIGNATURES_VAE22.items()) +
+                               list(SIGNATURES_ANIMATE.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, ctypes.c_int)

@@ -507,6 +507,60 @@ def relu(x):
     return x
 
 
+def face_attn(q, k, v, wq, out=None, *, batch, num_heads, frames, tokens_per_frame, nkeys, token_offset=0,
+              eps=1e-6, scale=None, head_dim=128):
+    """FaceBlock's attention (vs_face_attn): q [batch * rows_per_batch, >= H*128] rows, each attending the
+    nkeys keys of its latent frame with the per-head RMSNorm of q (weight wq [128]) fused in.  k, v:
+    [batch or 1, frames * nkeys, >= H*128] views sharing one row and one sample stride (k normalised by
+    head_rmsnorm).  out defaults to q (in place)."""
+    M, Dq, ldq = _rows(q, "q")
+    out = q if out is None else out
+    Mo, Do, ldo = _rows(out, "out")
+    width = num_heads * head_dim
+    if M % batch or Mo != M or Dq < width or Do < width:
+        raise ValueError(f"face_attn: q {tuple(q.shape)} / out {tuple(out.shape)} against batch {batch}, "
+                         f"{num_heads} heads")
+    _req(k, "k"), _req(v, "v"), _req(wq, "wq")
+    if k.dim() != 3 or k.shape != v.shape or k.stride() != v.stride() or k.stride(2) != 1 or \
+            k.shape[0] not in (1, batch) or k.shape[1] != frames * nkeys or k.shape[2] < width:
+        raise ValueError(f"face_attn: k {tuple(k.shape)} / v {tuple(v.shape)} are not [{batch} or 1, "
+                         f"{frames} * {nkeys}, >= {width}] views of one layout")
+    if wq.numel() != head_dim or not wq.is_contiguous():
+        raise ValueError(f"face_attn: wq must be contiguous [{head_dim}]")
+    kv_bs = 0 if k.shape[0] == 1 else k.stride(0)
+    sc = head_dim ** -0.5 if scale is None else scale
+    _lib.check(_lib.load().vs_face_attn(q.data_ptr(), ldq, k.data_ptr(), v.data_ptr(), k.stride(1), kv_bs,
+                                        out.data_ptr(), ldo, wq.data_ptr(), batch, M // batch, num_heads, head_dim,
+                                        frames, tokens_per_frame, nkeys, int(token_offset), float(eps), float(sc),
+                                        _stream(q)))
+    return out
+
+
+def head_rmsnorm(x, weight, num_heads, eps=1e-6, head_dim=128):
+    """The reference RMSNorm over each 128-wide head of every row of x, in place (vs_head_rmsnorm)."""
+    M, D, ldx = _rows(x, "x")
+    _req(weight, "weight")
+    if D < num_heads * head_dim or weight.numel() != head_dim or not weight.is_contiguous():
+        raise ValueError(f"head_rmsnorm: x {tuple(x.shape)} / weight {tuple(weight.shape)} against {num_heads} heads "
+                         f"of {head_dim}")
+    _lib.check(_lib.load().vs_head_rmsnorm(x.data_ptr(), ldx, M, num_heads, head_dim, weight.data_ptr(), float(eps),
+                                           _stream(x)))
+    return x
+
+
+def ln_silu(x, out=None, eps=1e-6, norm=True):
+    """out = bf16(silu(bf16(LayerNorm(x)))) without affine (vs_ln_silu); norm=False: SiLU alone.  In place
+    by default."""
+    M, D, ldx = _rows(x, "x")
+    out = x if out is None else out
+    Mo, Do, ldo = _rows(out, "out")
+    if (Mo, Do) != (M, D):
+        raise ValueError("ln_silu: shape mismatch")
+    _lib.check(_lib.load().vs_ln_silu(x.data_ptr(), ldx, out.data_ptr(), ldo, M, D, int(bool(norm)), float(eps),
+                                      _stream(x)))
+    return out
+
+
 def cfg_euler(v_pos, v_neg, x, cfg_scale, dsigma):
     for t, n in ((v_pos, "v_pos"), (x, "x")):
         _req(t, n)

@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from .models import DiTBlock, VaceWanModel, WanModel, block_fp8_linears
+from .models import ANIMATE_PREFIXES, DiTBlock, VaceWanModel, WanAnimateAdapter, WanModel, block_fp8_linears
 
 WAN_DIT_CONFIGS = {
     "9269f8db9040a9d860eaca435be61814": dict(dim=1536, ffn_dim=8960, num_heads=12, num_layers=30),   # 1.3B
@@ -58,6 +58,10 @@ WAN_FUN_DIT_CONFIGS = {
                                              in_dim_control_adapter=24,
                                              require_clip_embedding=False),           # Wan2.2-Fun-A14B-Control-Camera
 }
+# Wan2.2-Animate-14B (configs/model_config.py:179): the I2V-14B DiT's key set plus the adapter's 138 keys.  The
+# file is split as the reference's two converters split it (wan_video_dit.py:508,
+# wan_video_animate_adapter.py:664-669): the DiT part is looked up in the tables above.
+WAN_ANIMATE_HASH = "31fa352acb8a1b1d33cd8764273d80a2"
 WAN_COMMON = dict(in_dim=16, out_dim=16, text_dim=4096, freq_dim=256, eps=1e-6, patch_size=(1, 2, 2))
 VACE_14B_HASH = "3b2726384e4f64837bdf216eea3f310d"
 VACE_14B = dict(vace_layers=(0, 5, 10, 15, 20, 25, 30, 35), vace_in_dim=96, patch_size=(1, 2, 2),
@@ -249,6 +253,37 @@ def build_dit(state_dict, device):
     return model
 
 
+def split_animate(state_dict):
+    """(the state dict without the animate adapter's keys, the adapter's keys): the two from_civitai filters of
+    the reference (wan_video_dit.py:508, wan_video_animate_adapter.py:664-669).  A file without such keys
+    gives (state_dict, {})."""
+    ad = {k: v for k, v in state_dict.items() if isinstance(k, str) and k.startswith(ANIMATE_PREFIXES)}
+    if not ad:
+        return state_dict, {}
+    return {k: v for k, v in state_dict.items() if k not in ad}, ad
+
+
+def build_animate_adapter(adapter_sd, dit, device):
+    """WanAnimateAdapter of the DiT's (dim, num_heads, num_layers) from the adapter keys of a file; the face
+    encoder's in_dim off conv1_local's shape.  The motion_encoder.* tensors stay on the module unconverted."""
+    need = ("pose_patch_embedding.weight", "face_encoder.conv1_local.conv.weight",
+            "face_adapter.fuser_blocks.0.linear1_q.weight")
+    if not all(k in adapter_sd for k in need):
+        raise ValueError("animate adapter keys without pose_patch_embedding / face_encoder / face_adapter tensors")
+    dim = adapter_sd["pose_patch_embedding.weight"].shape[0]
+    n = _n_blocks({k[len("face_adapter."):]: v for k, v in adapter_sd.items() if k.startswith("face_adapter.")},
+                  "fuser_blocks")
+    L = len(dit.blocks)
+    if dim != dit.dim or n != -(-L // 5):
+        raise ValueError(f"the animate adapter (dim {dim}, {n} fuser blocks) does not fit the DiT (dim {dit.dim}, "
+                         f"{L} blocks: {-(-L // 5)} fuser blocks)")
+    model = WanAnimateAdapter(dim=dim, num_heads=dit.num_heads, num_layers=L,
+                              in_dim=adapter_sd["face_encoder.conv1_local.conv.weight"].shape[1], device=device)
+    model.load_state_dict({k: (v if k.startswith("motion_encoder.") else v.to(torch.bfloat16))
+                           for k, v in adapter_sd.items()}, strict=True)
+    return model
+
+
 def build_vace(state_dict, device, num_layers=None):
     sd = {k: v for k, v in state_dict.items() if k.startswith("vace")}
     if not sd:
@@ -362,7 +397,9 @@ def _check_experts(dits):
 
 def load_models(paths, device="cuda", fp8_weights="fold"):
     """Returns {'wan_video_dit': WanModel, 'wan_video_vace': VaceWanModel, ...} for the files given
-    ('wan_video_vae', 'wan_video_text_encoder' and 'wan_video_image_encoder' for those checkpoints).
+    ('wan_video_vae', 'wan_video_text_encoder' and 'wan_video_image_encoder' for those checkpoints;
+    'wan_video_animate_adapter' for a DiT file that also carries pose_patch_embedding. / face_adapter. /
+    face_encoder. / motion_encoder. keys, split off before the DiT's hash is taken).
     fp8_weights: "fold" -- e4m3 tensors become bf16 weights (upcast times scale_weight: normalize_keys)
     and nothing else; "keep" -- the same bf16 model (LoRA merge, hot-load and the bf16 layers work
     unchanged), whose block Linears additionally run the file's e4m3 bytes and scales on the fp8 GEMMs
@@ -383,7 +420,7 @@ def load_models(paths, device="cuda", fp8_weights="fold"):
     for path in paths:
         raw = load_state_dict(path, device="cpu")
         fp8 = fp8_checkpoint_tensors(raw) if fp8_weights == "keep" else {}
-        sd = normalize_keys(raw)
+        sd, animate_sd = split_animate(normalize_keys(raw))
         vae = build_vae(sd, device)
         if vae is not None:
             out["wan_video_vae"] = vae
@@ -407,6 +444,10 @@ def load_models(paths, device="cuda", fp8_weights="fold"):
                 raise ValueError(f"{path}: a third DiT checkpoint (a pipeline holds two experts, dit and dit2)")
             dits.append(dit)
             _check_experts(dits)
+            if animate_sd:
+                if "wan_video_animate_adapter" in out:
+                    raise ValueError(f"{path}: a second animate adapter")
+                out["wan_video_animate_adapter"] = build_animate_adapter(animate_sd, dit, device)
             vace = build_vace(sd, device, num_layers=len(dit.blocks))
             if vace is not None:
                 if len(vaces) == 2:

@@ -974,6 +974,192 @@ class VaceWanModel(nn.Module):
         return hints
 
 
+class CausalConv1dParams(nn.Module):
+    """wan_video_animate_adapter.py:50-63: Conv1d(cin, cout, 3) behind two replicate-padded frames, under
+    the reference's name `conv`.  Run as a GEMM over gathered rows: gemm_weight() is the weight as
+    (cout, Kp), column k cin + c = weight[:, c, k], Kp = 3 cin rounded up to the GEMM's K step of 64."""
+
+    def __init__(self, cin, cout, stride, device=None):
+        super().__init__()
+        self.cin, self.cout, self.stride = cin, cout, stride
+        self.conv = nn.Module()
+        self.conv.weight = _param(cout, cin, 3, device=device)
+        self.conv.bias = _param(cout, device=device)
+        self._w = self._w_of = None
+
+    def gemm_weight(self):
+        key = (self.conv.weight.data_ptr(), self.conv.weight._version)
+        if self._w is None or self._w_of != key:
+            k = 3 * self.cin
+            w = torch.zeros((self.cout, (k + 63) // 64 * 64), device=self.conv.weight.device, dtype=BF16)
+            w[:, :k].copy_(self.conv.weight.detach().permute(0, 2, 1).reshape(self.cout, k))
+            self._w, self._w_of = w, key
+        return self._w
+
+    def forward(self, x, tag, ws):
+        """x [G, T, cin] -> [G, T', cout], T' = (T - 1) // stride + 1: output frame t reads the frames
+        max(t stride + k - 2, 0), k = 0..2 (the row gather is indexing; the arithmetic is vs_gemm's)."""
+        G, T, C = x.shape
+        To = (T - 1) // self.stride + 1
+        w = self.gemm_weight()
+        src = (torch.arange(To, device=x.device).view(To, 1) * self.stride +
+               torch.arange(3, device=x.device).view(1, 3) - 2).clamp_(min=0)
+        cols = ws.get(tag + ".cols", (G * To, w.shape[1]))
+        if w.shape[1] != 3 * C:
+            cols.zero_()
+        cols.view(G, To, -1)[:, :, :3 * C].copy_(x[:, src].reshape(G, To, 3 * C))
+        out = ws.get(tag + ".out", (G * To, self.cout))
+        K.gemm(cols, w, out, bias=self.conv.bias)
+        return out.view(G, To, self.cout)
+
+
+class FaceEncoder(nn.Module):
+    """wan_video_animate_adapter.py:67-114: motion vectors [B, T, in_dim] -> [B, T', num_heads + 1,
+    hidden_dim] motion tokens (T' = T through strides 1, 2, 2), the last token of every frame the learned
+    padding token.  The three LayerNorms carry no parameters."""
+    WIDTH = 1024
+
+    def __init__(self, in_dim, hidden_dim, num_heads=4, device=None):
+        super().__init__()
+        self.in_dim, self.hidden_dim, self.num_heads = in_dim, hidden_dim, num_heads
+        self.conv1_local = CausalConv1dParams(in_dim, self.WIDTH * num_heads, 1, device)
+        self.conv2 = CausalConv1dParams(self.WIDTH, self.WIDTH, 2, device)
+        self.conv3 = CausalConv1dParams(self.WIDTH, self.WIDTH, 2, device)
+        self.out_proj = Linear(self.WIDTH, hidden_dim, device=device)
+        self.padding_tokens = _param(1, 1, 1, hidden_dim, device=device)
+
+    def forward(self, motion, ws):
+        B, T, C = motion.shape
+        if C != self.in_dim:
+            raise ValueError(f"face motion: expected [B, T, {self.in_dim}], got {tuple(motion.shape)}")
+        n, Wd = self.num_heads, self.WIDTH
+        x = self.conv1_local(motion.to(BF16), "face.c1", ws)                    # [B, T, n Wd]
+        # "b (n c) t -> (b n) t c": each head's 1024 channels become a sequence of their own
+        h = ws.get("face.h1", (B * n, T, Wd))
+        h.view(B, n, T, Wd).copy_(x.view(B, T, n, Wd).permute(0, 2, 1, 3))
+        K.ln_silu(h.view(-1, Wd))
+        x = self.conv2(h, "face.c2", ws)
+        K.ln_silu(x.view(-1, Wd))
+        x = self.conv3(x, "face.c3", ws)
+        K.ln_silu(x.view(-1, Wd))
+        To = x.shape[1]
+        y = ws.get("face.proj", (B * n * To, self.hidden_dim))
+        K.gemm(x.view(-1, Wd), self.out_proj.weight, y, bias=self.out_proj.bias)
+        out = torch.empty((B, To, n + 1, self.hidden_dim), device=motion.device, dtype=BF16)
+        out[:, :, :n].copy_(y.view(B, n, To, self.hidden_dim).permute(0, 2, 1, 3))
+        out[:, :, n] = self.padding_tokens.view(self.hidden_dim)
+        return out
+
+
+class FaceBlock(nn.Module):
+    """wan_video_animate_adapter.py:235-310 parameters (the two pre-norms carry none)."""
+
+    def __init__(self, dim, num_heads, device=None):
+        super().__init__()
+        self.dim, self.num_heads = dim, num_heads
+        self.linear1_kv = Linear(dim, 2 * dim, device=device)
+        self.linear1_q = Linear(dim, dim, device=device)
+        self.linear2 = Linear(dim, dim, device=device)
+        self.q_norm = RMSNormW(dim // num_heads, device)
+        self.k_norm = RMSNormW(dim // num_heads, device)
+
+
+class FaceAdapter(nn.Module):
+    def __init__(self, dim, num_heads, num_adapter_layers, device=None):
+        super().__init__()
+        self.fuser_blocks = nn.ModuleList([FaceBlock(dim, num_heads, device) for _ in range(num_adapter_layers)])
+
+
+ANIMATE_EVERY = 5       # a fuser block after every fifth DiT block (wan_video_animate_adapter.py:646)
+ANIMATE_PREFIXES = ("pose_patch_embedding.", "face_adapter.", "face_encoder.", "motion_encoder.")
+
+
+class WanAnimateAdapter(nn.Module):
+    """wan_video_animate_adapter.py:615-650 for any (dim, num_heads, num_layers): the pose latents' patch
+    embedding, the face encoder and ceil(num_layers / 5) fuser blocks, under the reference's parameter
+    names.  The motion encoder (face frames -> one 512-vector per frame) is not built: its tensors are kept
+    unconverted in `motion_encoder` and the pipeline takes the motion vectors themselves
+    (animate_face_motion=).
+
+    Once per call: pose_rows() (the residual rows of every step's patch-embedding GEMM), motion_tokens()
+    and face_kv() (every fuser block's keys and values, K already through k_norm).  Per step, after block i
+    with i % 5 == 0: after_block()."""
+
+    def __init__(self, dim=5120, num_heads=40, num_layers=40, in_dim=512, eps=1e-6, device=None):
+        super().__init__()
+        if dim // num_heads != 128 or dim % num_heads:
+            raise NotImplementedError("WanAnimateAdapter: head_dim must be 128")
+        self.dim, self.num_heads, self.num_layers, self.eps = dim, num_heads, num_layers, eps
+        self.pose_patch_embedding = PatchEmbed(16, dim, device)
+        self.face_adapter = FaceAdapter(dim, num_heads, -(-num_layers // ANIMATE_EVERY), device)
+        self.face_encoder = FaceEncoder(in_dim, dim, 4, device)
+        self.motion_encoder = {}
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        sd = dict(state_dict)
+        self.motion_encoder = {k: sd.pop(k) for k in list(sd) if k.startswith("motion_encoder.")}
+        return super().load_state_dict(sd, strict=strict, **kw)
+
+    def pose_rows(self, pose_latents, frames, ws):
+        """pose_latents [Bp, 16, frames - 1, H, W] -> [Bp * frames (H/2)(W/2), dim]: the pose patch
+        embedding's rows at latent frames 1.. of every sample, zeros at frame 0
+        (after_patch_embedding: x[:, :, 1:] += pose_patch_embedding(pose_latents)).  A tensor of its own."""
+        p = self.pose_patch_embedding
+        if pose_latents.dim() != 5 or pose_latents.shape[1] != 16 or pose_latents.shape[2] != frames - 1 or frames < 2:
+            raise ValueError(f"pose_latents {tuple(pose_latents.shape)}: expected [B, 16, {frames} - 1, H, W] "
+                             "(one latent frame fewer than the latents: frame 0 is the reference image's)")
+        Bp, C, T, H, W = pose_latents.shape
+        hw = (H // 2) * (W // 2)
+        tok, _ = p(pose_latents.to(device=p.weight.device, dtype=BF16), ws, "pose")
+        rows = torch.zeros((Bp, frames * hw, self.dim), device=tok.device, dtype=BF16)
+        rows[:, hw:].copy_(tok.view(Bp, T * hw, self.dim))
+        return rows.view(Bp * frames * hw, self.dim)
+
+    def motion_tokens(self, motion, ws):
+        """motion [B, T_face, in_dim] -> [B, T' + 1, N, dim]: the face encoder's tokens behind a zero frame
+        (after_patch_embedding's pad_face)."""
+        tok = self.face_encoder(motion.to(self.face_encoder.out_proj.weight.device), ws)
+        B, To, N, D = tok.shape
+        out = torch.zeros((B, To + 1, N, D), device=tok.device, dtype=BF16)
+        out[:, 1:].copy_(tok)
+        return out
+
+    def face_kv(self, motion_vec, ws):
+        """motion_vec [B, F, N, dim] -> one [B, F N, 2 dim] buffer per fuser block, columns [0, dim) the
+        keys after k_norm and [dim, 2 dim) the values: pre_norm_motion (LayerNorm without affine: the zero
+        frame stays zero), linear1_kv, the per-head RMSNorm of the K half.  The buffers belong to the
+        workspace: a captured step reads them and the next call of the same shape overwrites them."""
+        B, F, N, D = motion_vec.shape
+        rows = motion_vec.reshape(B * F * N, D).contiguous()
+        h = ws.get("animate.kv_h", (B * F * N, D))
+        K.layernorm_modulate(rows, h, self.eps)
+        out = []
+        for i, fb in enumerate(self.face_adapter.fuser_blocks):
+            kv = ws.get(f"animate.kv{i}", (B, F * N, 2 * D))
+            K.gemm(h, fb.linear1_kv.weight, kv.view(B * F * N, 2 * D), bias=fb.linear1_kv.bias)
+            K.head_rmsnorm(kv.view(B * F * N, 2 * D)[:, :D], fb.k_norm.weight, self.num_heads, self.eps)
+            out.append(kv)
+        return out
+
+    def after_block(self, i, x, kv, rc):
+        """after_transformer_block (:645-650) on the rows of x [B * S, dim] in place: LayerNorm without
+        affine, linear1_q, vs_face_attn against this fuser block's keys / values, linear2 with the residual
+        add fused.  Row-local: under Ulysses every rank runs it on its own rows (rc.token_offset)."""
+        if i % ANIMATE_EVERY:
+            return x
+        fb = self.face_adapter.fuser_blocks[i // ANIMATE_EVERY]
+        B, S, D, ws = rc.batch, rc.seq, self.dim, rc.ws
+        k = kv[i // ANIMATE_EVERY]
+        F, hw = rc.grid[0], rc.grid[1] * rc.grid[2]
+        h = ln_into(x, ws.get("h", (B * S, D)), ws, fb.linear1_q, self.eps)
+        q = ws.get("q", (B * S, D))
+        linear(fb.linear1_q, h, q, ws)
+        K.face_attn(q, k[:, :, :D], k[:, :, D:], fb.q_norm.weight, batch=B, num_heads=self.num_heads, frames=F,
+                    tokens_per_frame=hw, nkeys=k.shape[1] // F, token_offset=rc.token_offset, eps=self.eps)
+        linear(fb.linear2, q, x, ws, epilogue=K.VS_EPI_RES, residual=x)
+        return x
+
+
 def init_random_(module, seed=5, std=0.02):
     """Synthetic on-device init of SURVEY.md §8(d) (used by bench.py / smoke; real checkpoints load
     by name): N(0,std) weights, 0.01*N biases, modulation randn/sqrt(D), norm weights 1+0.1*N."""

@@ -31,8 +31,7 @@ def _workspace(device):
     return _WS[key]
 
 
-_UNSUPPORTED = ("audio_embeds", "motion_latents", "s2v_pose_latents", "motion_bucket_id", "pose_latents",
-                "face_pixel_values")
+_UNSUPPORTED = ("audio_embeds", "motion_latents", "s2v_pose_latents", "motion_bucket_id", "face_pixel_values")
 
 _WINDOW_PLANS = {}
 
@@ -102,7 +101,8 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
                        sp_group=None, slg_blocks=(), tea_cache=None, cfg_sample=0, sliding_window_size=None,
                        sliding_window_stride=None, vace_context_windows=None, y=None, clip_feature=None,
                        y_windows=None, fuse_vae_embedding_in_latents=False, reference_latents=None,
-                       control_camera_latents_input=None, reference_tokens=None, camera_tokens=None, **kwargs):
+                       control_camera_latents_input=None, reference_tokens=None, camera_tokens=None,
+                       pose_latents=None, pose_tokens=None, animate_face_motion=None, animate_kv=None, **kwargs):
     """One DiT(+VACE) forward (wan_video_new.py:1338-1468) -> [B,dit.out_dim,T,H,W] bf16 velocity.
 
     fuse_vae_embedding_in_latents (with dit.seperated_timestep: Wan2.2-TI2V-5B's image-to-video mode,
@@ -150,7 +150,44 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     camera_tokens [S or B S, D], which win over the raw inputs.  ValueError: a DiT without the module, a
     wrong shape, reference_latents together with a VACE context (the reference's token counts do not
     match there); NotImplementedError: camera control over more than one sliding window (the reference's
-    tiler drops it, :1292-1307)."""
+    tiler drops it, :1292-1307).
+
+    Wan2.2-Animate (animate_adapter: a WanAnimateAdapter of the DiT's width).  pose_latents [1 or B, 16,
+    T - 1, H, W]: their patch embedding is added to the tokens of latent frames 1.. in the patch-embedding
+    GEMM's epilogue (after_patch_embedding: bf16(x + bf16(pose))).  animate_face_motion [1 or B, T_face, 512]:
+    the motion vectors of the face frames (the reference's motion_encoder.get_motion output); the face
+    encoder turns them into N motion tokens per latent frame behind a zero frame, and after every fifth
+    block a FaceBlock cross-attends each frame's tokens to them (vs_face_attn).  Neither depends on the
+    timestep: a denoising loop computes them once (animate_pose_rows, animate_face_kv) and hands them over
+    as pose_tokens [S or B S, D] / animate_kv (one [B, T N, 2 D] buffer per fuser block), which win over the raw
+    inputs.  face_pixel_values is NotImplementedError (the motion encoder is not in this build).  With the
+    adapter's inputs these are NotImplementedError too: a sliding window of more than one window, tea_cache,
+    a VACE context, reference_latents, fuse_vae_embedding_in_latents, camera control, slg_blocks."""
+    use_pose = pose_latents is not None or pose_tokens is not None
+    use_face = animate_face_motion is not None or animate_kv is not None
+    if kwargs.get("face_pixel_values") is not None:
+        raise NotImplementedError("model_fn_wan_video: 'face_pixel_values' needs the motion encoder, which is not in "
+                                  "this build: pass the motion vectors as animate_face_motion=")
+    if use_pose or use_face:
+        if animate_adapter is None:
+            raise ValueError("model_fn_wan_video: pose_latents / animate_face_motion need animate_adapter= (a "
+                             "WanAnimateAdapter)")
+        if animate_adapter.dim != dit.dim or animate_adapter.num_heads != dit.num_heads or \
+                len(animate_adapter.face_adapter.fuser_blocks) != -(-len(dit.blocks) // 5):
+            raise ValueError("model_fn_wan_video: the animate adapter's dim, num_heads or fuser block count do not "
+                             "match the DiT")
+        w = check_window_args(sliding_window_size, sliding_window_stride)
+        what = ("a temporal sliding window of more than one window"
+                if w is not None and len(plan_windows(latents.shape[2], *w).windows) > 1 else
+                "tea_cache" if tea_cache is not None else
+                "a VACE context" if vace is not None and vace_context is not None else
+                "reference_latents" if reference_latents is not None or reference_tokens is not None else
+                "fuse_vae_embedding_in_latents (first_frame_latents)" if fuse_vae_embedding_in_latents else
+                "camera control" if control_camera_latents_input is not None or camera_tokens is not None else
+                "slg_blocks" if len(slg_blocks) else None)
+        if what is not None:
+            raise NotImplementedError(f"model_fn_wan_video: the animate adapter (pose_latents / animate_face_motion) "
+                                      f"with {what}")
     use_ref = reference_latents is not None or reference_tokens is not None
     use_cam = control_camera_latents_input is not None or camera_tokens is not None
     if use_ref:
@@ -236,6 +273,10 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
                                            control_camera_latents_input=control_camera_latents_input,
                                            reference_tokens=_mine_rows(reference_tokens, c, hw),
                                            camera_tokens=_mine_rows(camera_tokens, c, latents.shape[2] * hw),
+                                           pose_latents=mine(pose_latents),
+                                           pose_tokens=_mine_rows(pose_tokens, c, latents.shape[2] * hw),
+                                           animate_face_motion=mine(animate_face_motion),
+                                           animate_kv=None if animate_kv is None else [mine(kv) for kv in animate_kv],
                                            **kwargs)
                 out = torch.empty((2,) + tuple(local.shape[1:]), device=local.device, dtype=local.dtype)
                 plan.gather_cfg(out, local)
@@ -285,6 +326,36 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
             cam = ws.get("cam_rep", (B * S0, dit.dim)).view(B, S0, dit.dim).copy_(
                 cam.view(1, S0, dit.dim).expand(B, S0, dit.dim)).view(B * S0, dit.dim)
         extra["residual"] = cam
+    if use_pose:
+        Tl, hw0 = latents.shape[2], (latents.shape[3] // 2) * (latents.shape[4] // 2)
+        if pose_tokens is None:
+            if tuple(pose_latents.shape[3:]) != tuple(latents.shape[3:]):
+                raise ValueError(f"model_fn_wan_video: pose_latents {tuple(pose_latents.shape)} do not match latents "
+                                 f"{tuple(latents.shape)}")
+            pose_tokens = animate_adapter.pose_rows(pose_latents, Tl, ws)
+        S0 = Tl * hw0
+        if pose_tokens.dim() != 2 or pose_tokens.shape[1] != dit.dim or pose_tokens.shape[0] not in (S0, B * S0):
+            raise ValueError(f"model_fn_wan_video: pose_tokens {tuple(pose_tokens.shape)} are not [{S0} or {B} * {S0}, "
+                             f"{dit.dim}]")
+        if pose_tokens.shape[0] != B * S0:      # one pose for every CFG sample
+            pose_tokens = ws.get("pose_rep", (B * S0, dit.dim)).view(B, S0, dit.dim).copy_(
+                pose_tokens.view(1, S0, dit.dim).expand(B, S0, dit.dim)).view(B * S0, dit.dim)
+        elif B > 1:
+            shared = False                      # per-sample rows: block 0 sees different samples
+        extra["residual"] = pose_tokens
+    if use_face:
+        if animate_kv is None:
+            if animate_face_motion.dim() != 3 or animate_face_motion.shape[0] not in (1, B):
+                raise ValueError(f"model_fn_wan_video: animate_face_motion {tuple(animate_face_motion.shape)}: expected "
+                                 f"[1 or {B}, T_face, {animate_adapter.face_encoder.in_dim}]")
+            animate_kv = animate_adapter.face_kv(animate_adapter.motion_tokens(animate_face_motion, ws), ws)
+        Tl = latents.shape[2]
+        for kv in animate_kv:
+            if kv.dim() != 3 or kv.shape[0] not in (1, B) or kv.shape[1] % Tl or not 1 <= kv.shape[1] // Tl <= 8 or \
+                    kv.shape[2] != 2 * dit.dim:
+                raise ValueError(f"model_fn_wan_video: the face motion covers {tuple(kv.shape)} key rows: expected "
+                                 f"[1 or {B}, {Tl} latent frames * N (1..8), {2 * dit.dim}] (T_face frames give "
+                                 f"((T_face - 1) // 2) // 2 + 2 latent frames)")
     if use_ref:
         extra["skip"] = n_ref
     if y is None and not extra:
@@ -358,6 +429,8 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
             skip = B > 1 and i in slg_blocks
             blk(x, t_mod, rc, hint=hint, hint_scale=float(vace_scale), only_batch=0 if skip else None,
                 shared_prefix=shared and i == 0)
+            if use_face:                                        # after_transformer_block
+                animate_adapter.after_block(i, x, animate_kv, rc)
         if tea_cache is not None:
             tea_cache.store(x)                                  # :1455-1456
     out = dit.head(x, t, rc)
@@ -430,6 +503,54 @@ def fun_control_y(control_latents, y, clip_feature, in_dim, keep_clip=False):
     else:
         y = y[:, -y_dim:]
     return torch.cat([control_latents, y.to(control_latents.device)], dim=1).contiguous(), clip_feature
+
+
+def animate_i2v_mask(mask, h, w):
+    """get_i2v_mask of WanVideoPostUnit_AnimateInpaint (wan_video_new.py:1118-1127) with mask_len 0 on mask
+    pixel values [F, H, W] (already 1 - mask video): nearest-resized to the latent grid (:1145: row i reads row
+    floor(i H / h)), the first frame four times, then groups of four -> (4, (F + 3) / 4, h, w)."""
+    F_, H, W = mask.shape
+    if (F_ + 3) % 4:
+        raise ValueError(f"animate_mask_video: {F_} frames are not 4 k + 1")
+    ri = (torch.arange(h, device=mask.device) * H) // h
+    ci = (torch.arange(w, device=mask.device) * W) // w
+    m = mask[:, ri][:, :, ci]
+    m = torch.cat([m[0:1].expand(4, h, w), m[1:]], dim=0)
+    return m.view((F_ + 3) // 4, 4, h, w).transpose(0, 1).contiguous()
+
+
+def animate_inpaint_y(ref_latents, bg_latents, mask):
+    """The y of WanVideoPostUnit_AnimateInpaint (wan_video_new.py:1129-1151) from its encoded parts:
+    ref_latents (1, 16, 1, h, w) of input_image under a mask of ones (y_ref), then bg_latents (1, 16, T, h, w)
+    of the inpaint video under animate_i2v_mask(mask) (y_reft) -> (1, 20, 1 + T, h, w) bf16."""
+    _, _, T, h, w = bg_latents.shape
+    dev = bg_latents.device
+    y_ref = torch.cat([torch.ones((4, 1, h, w), device=dev, dtype=BF16), ref_latents[0].to(device=dev, dtype=BF16)])
+    msk = animate_i2v_mask(mask.to(dev), h, w).to(BF16)
+    if msk.shape[1] != T:
+        raise ValueError(f"animate_mask_video covers {msk.shape[1]} latent frames, animate_inpaint_video {T}")
+    y_reft = torch.cat([msk, bg_latents[0].to(BF16)])
+    return torch.cat([y_ref, y_reft], dim=1).unsqueeze(0).contiguous()
+
+
+def animate_face_motion_batch(motion, motion_uncond, use_cfg):
+    """The face motion of a step's batch: motion [T_face, C] or [1, T_face, C]; with CFG the unconditioned
+    sample's rows behind it -- motion_uncond [C], [1, C] (one vector, the motion of the reference's constant
+    -1 face frame, broadcast over time), [T_face, C] or [1, T_face, C].  -> [1 or 2, T_face, C]."""
+    m = motion if motion.dim() == 3 else motion[None]
+    if m.dim() != 3 or m.shape[0] != 1:
+        raise ValueError(f"animate_face_motion: expected [T_face, C] or [1, T_face, C], got {tuple(motion.shape)}")
+    if not use_cfg:
+        return m
+    if motion_uncond is None:
+        raise ValueError("animate_face_motion with cfg_scale != 1 needs animate_face_motion_uncond= (the motion "
+                         "vector of the reference's constant -1 face frame, which its unconditioned sample sees)")
+    u = motion_uncond.to(m.device)
+    T, C = m.shape[1], m.shape[2]
+    if u.shape[-1] != C or u.numel() not in (C, T * C):
+        raise ValueError(f"animate_face_motion_uncond: expected [{C}] or [{T}, {C}], got {tuple(motion_uncond.shape)}")
+    u = u.reshape(1, -1, C).expand(1, T, C)
+    return torch.cat([m, u.to(m.dtype)], dim=0)
 
 
 def image_mask(num_frames, h, w, has_end=False, device=None, dtype=BF16):
@@ -696,6 +817,7 @@ class WanVideoPipeline:
         # the second expert of a Wan2.2 A14B pair, in file order (fetch_model(..., index=2), :381-391)
         pipe.dit2 = models.get("wan_video_dit2")
         pipe.vace2 = models.get("wan_video_vace2")
+        pipe.animate_adapter = models.get("wan_video_animate_adapter")
         pipe.vae = models.get("wan_video_vae")
         pipe.text_encoder = models.get("wan_video_text_encoder")
         pipe.image_encoder = models.get("wan_video_image_encoder")
@@ -795,8 +917,16 @@ class WanVideoPipeline:
                 num_inference_steps=50, sigma_shift=5.0, denoising_strength=1.0, progress_bar_cmd=None,
                 use_graph=None, tea_cache=None, sliding_window_size=None, sliding_window_stride=None,
                 switch_DiT_boundary=0.875, y=None, clip_feature=None, first_frame_latents=None,
-                reference_latents=None, control_camera_latents_input=None):
+                reference_latents=None, control_camera_latents_input=None, pose_latents=None,
+                animate_face_motion=None, animate_face_motion_uncond=None):
         """The loop of wan_video_new.py:515-542 (cfg_merge batched), returns the final latents.
+
+        pose_latents [1, 16, T - 1, h, w] / animate_face_motion [1, T_face, 512] (Wan2.2-Animate, with
+        pipe.animate_adapter; model_fn_wan_video): computed once before the loop -- the pose rows, the face
+        encoder and every fuser block's keys and values, which live in workspace buffers that the captured
+        step reads and the next call overwrites.  With CFG the unconditioned sample attends the keys of
+        animate_face_motion_uncond (required then).  NotImplementedError with a sliding window, tea_cache, dit2,
+        VACE, reference_latents or first_frame_latents.
 
         reference_latents [1, 16, (1,) h, w] / control_camera_latents_input [1, 24, T, H, W] (Wan-Fun
         control, model_fn_wan_video): neither depends on the step, so each expert's ref_conv tokens and
@@ -836,6 +966,12 @@ class WanVideoPipeline:
         if has2 and tea_cache is not None:
             # the reference hands one TeaCache state to both experts and has no coefficients for them
             raise NotImplementedError("tea_cache_l1_thresh with a second expert (dit2) is not supported")
+        animate = pose_latents is not None or animate_face_motion is not None
+        if animate:
+            win = check_window_args(sliding_window_size, sliding_window_stride)
+            multi = win is not None and len(plan_windows(latents.shape[2], *win).windows) > 1
+            self._check_animate(multi, tea_cache, vace_context, reference_latents, first_frame_latents,
+                                control_camera_latents_input)
         window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context,
                                         tea_cache, y=y)
         image_kw = self._image_kwargs(y, clip_feature)
@@ -867,6 +1003,9 @@ class WanVideoPipeline:
             ctx = ctx_cfg if use_cfg else context_posi
             control_kw = self._control_kwargs(dit, reference_latents, control_camera_latents_input,
                                               2 if use_cfg else 1)
+            if animate:
+                control_kw.update(self._animate_kwargs(pose_latents, animate_face_motion, animate_face_motion_uncond,
+                                                       use_cfg, latents.shape[2]))
 
             def step(t_buf, d_buf):
                 v = self.model_fn(dit=dit, vace=vace, latents=latents, timestep=t_buf, context=ctx,
@@ -929,6 +1068,34 @@ class WanVideoPipeline:
                 raise ValueError("camera control needs a DiT with control_adapter (add_control_adapter); with two "
                                  "experts, both")
 
+    def _check_animate(self, windows, tea_cache, vace_context, reference_latents, first_frame_latents,
+                       control_camera_latents_input):
+        """The Wan2.2-Animate inputs of a loop against the rest of the call, before anything is computed."""
+        if self.animate_adapter is None:
+            raise ValueError("pose_latents / animate_face_motion need pipe.animate_adapter (a Wan2.2-Animate checkpoint)")
+        what = ("a temporal sliding window" if windows else
+                "tea_cache" if tea_cache is not None else
+                "a second expert (dit2)" if self.dit2 is not None else
+                "VACE" if vace_context is not None and self.vace is not None else
+                "reference_latents" if reference_latents is not None else
+                "first_frame_latents" if first_frame_latents is not None else
+                "camera control" if control_camera_latents_input is not None else None)
+        if what is not None:
+            raise NotImplementedError(f"the animate adapter (pose_latents / animate_face_motion) with {what} is not "
+                                      f"supported")
+
+    def _animate_kwargs(self, pose_latents, motion, motion_uncond, use_cfg, frames):
+        """model_fn's Wan2.2-Animate constants, computed here once per call: the pose rows (one set for every
+        CFG sample), and every fuser block's K / V from the face motion of the step's batch."""
+        ad, ws = self.animate_adapter, _workspace(self.device)
+        kw = {"animate_adapter": ad}
+        if pose_latents is not None:
+            kw["pose_tokens"] = ad.pose_rows(pose_latents.to(self.device), frames, ws)
+        if motion is not None:
+            m = animate_face_motion_batch(motion.to(self.device), motion_uncond, use_cfg)
+            kw["animate_kv"] = ad.face_kv(ad.motion_tokens(m, ws), ws)
+        return kw
+
     def _control_kwargs(self, dit, reference_latents, control_camera_latents_input, batch):
         """model_fn's Wan-Fun constants of one expert ({} without them): its ref_conv tokens and its camera
         adapter rows replicated over the step's batch, computed here once."""
@@ -970,7 +1137,8 @@ class WanVideoPipeline:
                       progress_bar_cmd=None, input_latents=None, forward_step=None, skip_backward_step=None,
                       sliding_window_size=None, sliding_window_stride=None, switch_DiT_boundary=0.875,
                       y=None, clip_feature=None, first_frame_latents=None, reference_latents=None,
-                      control_camera_latents_input=None):
+                      control_camera_latents_input=None, pose_latents=None, animate_face_motion=None,
+                      animate_face_motion_uncond=None):
         """Config 5's sampler (ditto_comfyui_workflow.json WanVideoSampler 4 / 1.2 / 2.0 / unipc with
         WanVideoSLG): FlowUniPCMultistepScheduler (vstyler.unipc) on fp32 latents, CFG as one
         batch-2 forward, skip-layer guidance on the uncond sample for step fractions in slg_range.
@@ -989,6 +1157,9 @@ class WanVideoPipeline:
         (low_noise, high_noise) pair as in denoise.  An expert no executed step selects is never
         touched: the Wan2.2 enhancer pass (40 steps, shift 12, forward_step = skip_backward_step = 5)
         has every timestep below 875 and runs with pipe.dit = None."""
+        if pose_latents is not None or animate_face_motion is not None:
+            raise NotImplementedError("the animate adapter (pose_latents / animate_face_motion) with the UniPC sampler "
+                                      "is not supported: use denoise (Euler)")
         from .experts import expert_cfg_scales, plan_experts
         if first_frame_latents is not None:
             raise ValueError("first_frame_latents is not supported by the UniPC sampler (use denoise)")
@@ -1064,8 +1235,20 @@ class WanVideoPipeline:
                  # extensions of this build (the DiT path without T5/VAE):
                  prompt_emb=None, negative_prompt_emb=None, vace_context=None, output_type="video",
                  input_latents=None, clip_feature=None, first_frame_latents=None, control_latents=None,
-                 reference_latents=None, control_camera_latents_input=None, **kwargs):
-        """Wan-Fun control (WanVideoUnit_FunControl / FunReference / FunCameraControl, wan_video_new.py:752-845,
+                 reference_latents=None, control_camera_latents_input=None, animate_pose_video=None,
+                 animate_face_video=None, animate_inpaint_video=None, animate_mask_video=None, pose_latents=None,
+                 animate_face_motion=None, animate_face_motion_uncond=None, **kwargs):
+        """Wan2.2-Animate (WanVideoPostUnit_AnimatePoseLatents / AnimateFacePixelValues / AnimateInpaint,
+        wan_video_new.py:1083-1151) with pipe.animate_adapter and input_image.  animate_pose_video (num_frames - 4
+        frames; or its latents pose_latents [1, 16, T' - 1, h, w]) is VAE-encoded and patch-embedded onto the
+        latent frames 1..; animate_face_motion [T_face, 512] are the face frames' motion vectors (the reference's
+        motion encoder output; T_face = num_frames - 4) and animate_face_motion_uncond the vector of its constant
+        -1 face frame, required with CFG.  animate_face_video itself is NotImplementedError: the motion encoder is
+        not in this build.  animate_inpaint_video + animate_mask_video (num_frames - 4 frames each) replace y by the
+        inpaint form (animate_inpaint_y).  With both a pose and a face motion the first latent frame is dropped
+        before decoding (:545-550), so the video has num_frames - 4 frames.
+
+        Wan-Fun control (WanVideoUnit_FunControl / FunReference / FunCameraControl, wan_video_new.py:752-845,
         in the reference's unit order).  control_video (or its precomputed control_latents [1, 16, T', h, w]):
         VAE-encoded and put in front of y, whose other in_dim - 32 channels are the last ones of the image y
         when input_image gave both y and CLIP features, else zeros -- clip_feature then defaults to zeros
@@ -1095,6 +1278,20 @@ class WanVideoPipeline:
         of the shortened schedule (WanVideoUnit_InputVideoEmbedder, :591-614)."""
         if motion_bucket_id is not None:
             raise NotImplementedError("motion_bucket_id is outside the Ditto hot path of this build")
+        if animate_face_video is not None:
+            raise NotImplementedError("animate_face_video needs the motion encoder, which is not in this build: pass "
+                                      "the face frames' motion vectors as animate_face_motion= [T_face, 512] (and "
+                                      "animate_face_motion_uncond= with CFG)")
+        has_pose = animate_pose_video is not None or pose_latents is not None
+        has_animate = has_pose or animate_face_motion is not None or animate_inpaint_video is not None or \
+            animate_mask_video is not None
+        if has_animate:
+            if self.animate_adapter is None:
+                raise ValueError("the animate_* arguments need pipe.animate_adapter (a Wan2.2-Animate checkpoint)")
+            if input_image is None:
+                raise ValueError("the animate_* arguments need input_image (the character's reference image)")
+            if (animate_inpaint_video is None) != (animate_mask_video is None):
+                raise ValueError("animate_inpaint_video and animate_mask_video go together")
         fused = self.dit is not None and self.dit.fuse_vae_embedding_in_latents
         fused_image = None                                  # WanVideoUnit_ImageEmbedderFused's image (below)
         if input_image is not None and fused:
@@ -1148,8 +1345,14 @@ class WanVideoPipeline:
             vace_context = self.encode_vace(vace_video, vace_video_mask, height, width, num_frames, tiled,
                                             tile_size, tile_stride, vace_reference_image)
         y = None
-        if input_image is not None:
+        if input_image is not None and animate_inpaint_video is not None:     # WanVideoPostUnit_AnimateInpaint
+            y = self.encode_animate_inpaint(input_image, animate_inpaint_video, animate_mask_video, height, width,
+                                            num_frames, tiled, tile_size, tile_stride)
+        elif input_image is not None:
             y = self.encode_input_image(input_image, end_image, num_frames, height, width, tiled, tile_size, tile_stride)
+        if animate_pose_video is not None and pose_latents is None:           # WanVideoPostUnit_AnimatePoseLatents
+            pose_latents = self.encode_animate_video(animate_pose_video, "animate_pose_video", height, width,
+                                                     num_frames, tiled, tile_size, tile_stride)
         # WanVideoUnit_ImageEmbedderCLIP (wan_video_new.py:682-693); an explicit clip_feature= wins
         explicit_clip = clip_feature is not None
         if clip_feature is None and input_image is not None and self.image_encoder is not None and \
@@ -1185,10 +1388,14 @@ class WanVideoPipeline:
                                sliding_window_stride=sliding_window_stride, switch_DiT_boundary=switch_DiT_boundary,
                                y=y, clip_feature=clip_feature, first_frame_latents=first_frame_latents,
                                reference_latents=reference_latents,
-                               control_camera_latents_input=control_camera_latents_input)
+                               control_camera_latents_input=control_camera_latents_input, pose_latents=pose_latents,
+                               animate_face_motion=animate_face_motion,
+                               animate_face_motion_uncond=animate_face_motion_uncond)
         self.last_tea_cache = tea_cache
         if nref:                                            # :545-550
             latents = latents[:, :, nref:].contiguous()
+        elif has_pose and animate_face_motion is not None:  # :545-550: the reference image's frame
+            latents = latents[:, :, 1:].contiguous()
         if output_type == "latents":
             return latents
         if self.vae is None:
@@ -1368,6 +1575,39 @@ class WanVideoPipeline:
             raise ValueError(f"control_video must be {num_frames} frames of {height}x{width}, got {tuple(frames.shape)}")
         return self.vae.encode(preprocess_video(frames), self.device, tiled=tiled, tile_size=tile_size,
                                tile_stride=tile_stride).to(self.torch_dtype)
+
+    def encode_animate_video(self, video, name, height, width, num_frames, tiled=True, tile_size=(30, 52),
+                             tile_stride=(15, 26)):
+        """A driving video of Wan2.2-Animate (pose / inpaint: num_frames - 4 frames, one latent frame fewer than
+        the latents) -> (1, 16, T' - 1, h, w) bf16 (wan_video_new.py:1094-1095, :1134-1135)."""
+        from .vae import frames_to_u8, preprocess_video
+        if self.vae is None:
+            raise RuntimeError(f"{name} encoding requires a loaded Wan2.1 VAE")
+        frames = frames_to_u8(video, self.device)
+        if tuple(frames.shape) != (num_frames - 4, height, width, 3):
+            raise ValueError(f"{name} must be {num_frames - 4} frames (num_frames - 4) of {height}x{width}, got "
+                             f"{tuple(frames.shape)}")
+        return self.vae.encode(preprocess_video(frames), self.device, tiled=tiled, tile_size=tile_size,
+                               tile_stride=tile_stride).to(self.torch_dtype)
+
+    def encode_animate_inpaint(self, input_image, inpaint_video, mask_video, height, width, num_frames, tiled=True,
+                               tile_size=(30, 52), tile_stride=(15, 26)):
+        """WanVideoPostUnit_AnimateInpaint (wan_video_new.py:1129-1151) -> y (1, 20, T', h, w) bf16: the reference
+        image's latents under a mask of ones, then the inpaint video's under 1 - mask video (channel 0 of its
+        frames scaled to [0, 1]), nearest-resized to the latent grid."""
+        from .vae import frames_to_u8
+        bg = self.encode_animate_video(inpaint_video, "animate_inpaint_video", height, width, num_frames, tiled,
+                                       tile_size, tile_stride)
+        frame = self._image_frame(input_image, "input_image", height, width)
+        ref = self.vae.encode(frame.to(self.torch_dtype), self.device, tiled=tiled, tile_size=tile_size,
+                              tile_stride=tile_stride).to(self.torch_dtype)
+        m8 = frames_to_u8(mask_video, self.device)
+        if tuple(m8.shape) != (num_frames - 4, height, width, 3):
+            raise ValueError(f"animate_mask_video must be {num_frames - 4} frames (num_frames - 4) of {height}x{width}, "
+                             f"got {tuple(m8.shape)}")
+        m = (m8[..., 0].float() * (1.0 / 255)).to(self.torch_dtype)    # preprocess_video(max_value=1, min_value=0)
+        m = (1 - m.float()).to(self.torch_dtype)                        # :1143, a bf16 tensor op
+        return animate_inpaint_y(ref, bg, m)
 
     def encode_reference_image(self, reference_image, height, width):
         """WanVideoUnit_FunReference's reference_latents (wan_video_new.py:788-790) -> (1, 16, 1, h, w): the

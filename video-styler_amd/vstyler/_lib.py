@@ -1,5 +1,5 @@
 """ctypes binding of libvstyler.so (the C ABI declared in include/vstyler.h, vstyler_image.h,
-vstyler_clip.h, vstyler_seg.h, vstyler_control.h, vstyler_vae22.h and vstyler_animate.h).
+vstyler_clip.h, vstyler_seg.h, vstyler_control.h, vstyler_vae22.h, vstyler_animate.h and vstyler_motion.h).
 
 The product path has no CPU fallback: if the library is missing every op raises.
 """
@@ -160,6 +160,14 @@ SIGNATURES_ANIMATE = {
     "vs_head_rmsnorm": [_P, _LL, _I, _I, _I, _P, _F, _P],
     "vs_ln_silu": [_P, _LL, _P, _LL, _I, _I, _I, _F, _P],
 }
+# Wan2.2-Animate's motion encoder: the stem, FusedLeakyReLU fused into the blur and the ResBlock merge,
+# Direction (include/vstyler_motion.h): an eighth table
+SIGNATURES_MOTION = {
+    "vs_motion_stem": [_P, _I, _P, _P, _P, _LL, _LL, _I, _I, _I, _I, _P],
+    "vs_lrelu_blur": [_P, _LL, _LL, _P, _LL, _LL, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vs_lrelu_merge": [_P, _LL, _LL, _P, _P, _LL, _LL, _P, _LL, _LL, _I, _LL, _I, _P],
+    "vs_motion_direction": [_P, _LL, _P, _LL, _P, _LL, _I, _I, _I, _P],
+}
 _RESTYPES = {"vs_strerror": ctypes.c_char_p, "vs_split_workspace_bytes": ctypes.c_longlong,
              "vs_sp_last_error": ctypes.c_char_p}
 
@@ -178,7 +186,7 @@ def load():
         for name, argtypes in (list(SIGNATURES.items()) + list(SIGNATURES_IMAGE.items()) +
                                list(SIGNATURES_CLIP.items()) + list(SIGNATURES_SEG.items()) +
                                list(SIGNATURES_CONTROL.items()) + list(SIGNATURES_VAE22.items()) +
-                               list(SIGNATURES_ANIMATE.items())):
+                               list(SIGNATURES_ANIMATE.items()) + list(SIGNATURES_MOTION.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, ctypes.c_int)

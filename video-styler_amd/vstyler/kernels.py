@@ -561,6 +561,85 @@ def ln_silu(x, out=None, eps=1e-6, norm=True):
     return out
 
 
+def _frames(t, name, c=None):
+    """(n, H, W, frame stride, pixel stride) of a channels-last [n, H, W, >= c] bf16 view whose pixels of a
+    frame are evenly spaced (include/vstyler_motion.h: frames ns apart, pixels ld apart)."""
+    _req(t, name)
+    if t.dim() != 4 or t.stride(3) != 1 or t.stride(1) != t.shape[2] * t.stride(2):
+        raise ValueError(f"{name}: expected a channels-last [n, H, W, C] view with evenly spaced pixels, got "
+                         f"{tuple(t.shape)} strides {tuple(t.stride())}")
+    if c is not None and t.shape[3] != c:
+        raise ValueError(f"{name}: expected {c} channels, got {t.shape[3]}")
+    return t.shape[0], t.shape[1], t.shape[2], t.stride(0), t.stride(2)
+
+
+def motion_stem(frames, weight, bias, out):
+    """The motion encoder's stem (vs_motion_stem): frames uint8 [n, H, W, 3] or bf16 planar [3, n, H, W];
+    weight bf16 [c0, 3] (prepared), bias bf16 [c0]; out channels-last [n, H, W, c0]."""
+    n, H, W, ns, ld = _frames(out, "out")
+    c0 = out.shape[3]
+    u8 = frames.dtype == torch.uint8
+    want = (n, H, W, 3) if u8 else (3, n, H, W)
+    if frames.dtype not in (torch.uint8, BF16) or not frames.is_cuda or not frames.is_contiguous() or \
+            tuple(frames.shape) != want:
+        raise ValueError(f"motion_stem: frames must be contiguous uint8 [n, H, W, 3] or bfloat16 [3, n, H, W] on the "
+                         f"device matching out {tuple(out.shape)}, got {tuple(frames.shape)} {frames.dtype}")
+    _req(weight, "weight"), _req(bias, "bias")
+    if tuple(weight.shape) != (c0, 3) or not weight.is_contiguous() or bias.numel() != c0 or not bias.is_contiguous():
+        raise ValueError(f"motion_stem: weight {tuple(weight.shape)} / bias {tuple(bias.shape)} against {c0} channels")
+    _lib.check(_lib.load().vs_motion_stem(frames.data_ptr(), int(u8), weight.data_ptr(), bias.data_ptr(),
+                                          out.data_ptr(), ns, ld, n, H, W, c0, _stream(out)))
+    return out
+
+
+def lrelu_blur(x, out, bias=None, pad=(2, 2), step=1):
+    """out = Blur(pad)(ACT(x, bias))[::step, ::step] (vs_lrelu_blur; bias None: the blur alone).  x [n, H, W, C],
+    out [n, ceil((H + p0 + p1 - 3) / step), ceil((W + p0 + p1 - 3) / step), C], channels-last views."""
+    n, H, W, xns, ldx = _frames(x, "x")
+    c = x.shape[3]
+    no, Ho, Wo, yns, ldy = _frames(out, "out", c)
+    p0, p1 = pad
+    if step not in (1, 2) or (no, Ho, Wo) != (n, -(-(H + p0 + p1 - 3) // step), -(-(W + p0 + p1 - 3) // step)):
+        raise ValueError(f"lrelu_blur: out {tuple(out.shape)} against x {tuple(x.shape)}, pad {pad}, step {step}")
+    if bias is not None and (_req(bias, "bias").numel() != c or not bias.is_contiguous()):
+        raise ValueError(f"lrelu_blur: bias {tuple(bias.shape)} against {c} channels")
+    _lib.check(_lib.load().vs_lrelu_blur(x.data_ptr(), xns, ldx, out.data_ptr(), yns, ldy, _ptr(bias), n, H, W, c,
+                                         int(p0), int(p1), int(step), _stream(x)))
+    return out
+
+
+def lrelu_merge(x, bias, skip=None, out=None):
+    """out = ACT(x, bias), with skip: bf16(bf16(ACT(x, bias) + skip) / sqrt(2)) (vs_lrelu_merge).  Channels-last
+    [n, H, W, C] views; in place on x by default."""
+    n, H, W, xns, ldx = _frames(x, "x")
+    c = x.shape[3]
+    out = x if out is None else out
+    geo = _frames(out, "out", c)
+    sns = lds = 0
+    if skip is not None:
+        sgeo = _frames(skip, "skip", c)
+        if sgeo[:3] != (n, H, W):
+            raise ValueError(f"lrelu_merge: skip {tuple(skip.shape)} against x {tuple(x.shape)}")
+        sns, lds = sgeo[3], sgeo[4]
+    if geo[:3] != (n, H, W) or _req(bias, "bias").numel() != c or not bias.is_contiguous():
+        raise ValueError(f"lrelu_merge: out {tuple(out.shape)} / bias {tuple(bias.shape)} against x {tuple(x.shape)}")
+    _lib.check(_lib.load().vs_lrelu_merge(x.data_ptr(), xns, ldx, bias.data_ptr(), _ptr(skip), sns, lds,
+                                          out.data_ptr(), geo[3], geo[4], n, H * W, c, _stream(x)))
+    return out
+
+
+def motion_direction(alpha, q, out):
+    """out[t, j] = bf16(sum_i bf16(alpha[t, i] q[j, i])) (vs_motion_direction): alpha [T, m], q [d, m], out [T, d]."""
+    T, m, lda = _rows(alpha, "alpha")
+    d, mq, ldq = _rows(q, "q")
+    To, do, ldo = _rows(out, "out")
+    if mq != m or (To, do) != (T, d):
+        raise ValueError(f"motion_direction: alpha {tuple(alpha.shape)} / q {tuple(q.shape)} / out {tuple(out.shape)}")
+    _lib.check(_lib.load().vs_motion_direction(alpha.data_ptr(), lda, q.data_ptr(), ldq, out.data_ptr(), ldo, T, d, m,
+                                               _stream(out)))
+    return out
+
+
 def cfg_euler(v_pos, v_neg, x, cfg_scale, dsigma):
     for t, n in ((v_pos, "v_pos"), (x, "x")):
         _req(t, n)

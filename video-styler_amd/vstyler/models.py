@@ -1077,8 +1077,9 @@ ANIMATE_PREFIXES = ("pose_patch_embedding.", "face_adapter.", "face_encoder.", "
 class WanAnimateAdapter(nn.Module):
     """wan_video_animate_adapter.py:615-650 for any (dim, num_heads, num_layers): the pose latents' patch
     embedding, the face encoder and ceil(num_layers / 5) fuser blocks, under the reference's parameter
-    names.  The motion encoder (face frames -> one 512-vector per frame) is not built: its tensors are kept
-    unconverted in `motion_encoder` and the pipeline takes the motion vectors themselves
+    names.  The motion encoder's tensors (face frames -> one 512-vector per frame) are kept unconverted in
+    `motion_encoder`; encode_motion() builds vstyler.motion.MotionEncoder from them on first use, and the
+    pipeline takes either the face frames (animate_face_video=) or the motion vectors themselves
     (animate_face_motion=).
 
     Once per call: pose_rows() (the residual rows of every step's patch-embedding GEMM), motion_tokens()
@@ -1099,6 +1100,36 @@ class WanAnimateAdapter(nn.Module):
         sd = dict(state_dict)
         self.motion_encoder = {k: sd.pop(k) for k in list(sd) if k.startswith("motion_encoder.")}
         return super().load_state_dict(sd, strict=strict, **kw)
+
+    @property
+    def motion_encoder(self):
+        """The raw `motion_encoder.*` tensors, unconverted.  Assigning another dict drops the encoder built from
+        the previous one (`motion_net`)."""
+        return self.__dict__["_motion_encoder"]
+
+    @motion_encoder.setter
+    def motion_encoder(self, tensors):
+        self.__dict__["_motion_encoder"] = tensors
+        self.__dict__.pop("motion_net", None)
+
+    def motion_size(self):
+        """The face frame size of the motion encoder whose complete key set `motion_encoder` holds, or None."""
+        from .motion import size_of
+        return size_of(self.motion_encoder)
+
+    def encode_motion(self, frames, chunk=None):
+        """Face frames (uint8 [T, size, size, 3] or bf16 [3, T, size, size]) -> motion vectors [T, 512] bf16
+        (vstyler.motion.MotionEncoder, the reference's motion_encoder.get_motion).  The encoder is built from
+        the raw `motion_encoder` tensors on first use and kept as the plain attribute `motion_net` (no
+        registered submodule: state_dict() stays without its keys).  NotImplementedError when those tensors
+        are absent or incomplete."""
+        from .motion import ENCODE_BS, MotionEncoder
+        net = self.__dict__.get("motion_net")
+        if net is None or net.source_keys != len(self.motion_encoder):        # (a dict edited in place, too)
+            net = MotionEncoder(self.motion_encoder, device=self.face_encoder.out_proj.weight.device)
+            net.source_keys = len(self.motion_encoder)
+            self.__dict__["motion_net"] = net
+        return net.encode(frames, ENCODE_BS if chunk is None else chunk)
 
     def pose_rows(self, pose_latents, frames, ws):
         """pose_latents [Bp, 16, frames - 1, H, W] -> [Bp * frames (H/2)(W/2), dim]: the pose patch

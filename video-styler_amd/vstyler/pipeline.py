@@ -31,7 +31,7 @@ def _workspace(device):
     return _WS[key]
 
 
-_UNSUPPORTED = ("audio_embeds", "motion_latents", "s2v_pose_latents", "motion_bucket_id", "face_pixel_values")
+_UNSUPPORTED = ("audio_embeds", "motion_latents", "s2v_pose_latents", "motion_bucket_id")
 
 _WINDOW_PLANS = {}
 
@@ -93,6 +93,23 @@ def _windowed_forward(size, stride, dit, motion_controller, vace, animate_adapte
             value = torch.zeros((out.shape[0], out.shape[1], T, H, W), device=device, dtype=BF16)
         K.window_blend(out, masks[i], value, t)
     return K.window_finish(value, weight)
+
+
+def _encode_face_pixels(adapter, pixels, motion, kv):
+    """model_fn's face_pixel_values [B, 3, T_face, size, size] -> animate_face_motion [B, T_face, 512] through the
+    adapter's motion encoder, sample by sample (after_patch_embedding, wan_video_animate_adapter.py:627-637)."""
+    size = None if adapter is None else adapter.motion_size()
+    if size is None:
+        raise NotImplementedError("model_fn_wan_video: 'face_pixel_values' needs animate_adapter= with the complete "
+                                  "motion-encoder weights (motion_encoder.*): pass the motion vectors as "
+                                  "animate_face_motion=")
+    if motion is not None or kv is not None:
+        raise ValueError("model_fn_wan_video: pass face_pixel_values or its motion vectors (animate_face_motion / "
+                         "animate_kv), not both")
+    if pixels.dim() != 5 or pixels.shape[1] != 3 or tuple(pixels.shape[3:]) != (size, size):
+        raise ValueError(f"model_fn_wan_video: face_pixel_values {tuple(pixels.shape)}: expected [B, 3, T_face, {size}, "
+                         f"{size}] (the motion encoder's size; the reference does not resize either)")
+    return torch.stack([adapter.encode_motion(p.to(BF16)) for p in pixels])
 
 
 def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel = None, animate_adapter=None,
@@ -160,14 +177,17 @@ def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel
     block a FaceBlock cross-attends each frame's tokens to them (vs_face_attn).  Neither depends on the
     timestep: a denoising loop computes them once (animate_pose_rows, animate_face_kv) and hands them over
     as pose_tokens [S or B S, D] / animate_kv (one [B, T N, 2 D] buffer per fuser block), which win over the raw
-    inputs.  face_pixel_values is NotImplementedError (the motion encoder is not in this build).  With the
+    inputs.  face_pixel_values [B, 3, T_face, size, size] (the reference's input, in [-1, 1]) is encoded per
+    sample by the adapter's motion encoder (encode_motion) and proceeds as animate_face_motion; it excludes
+    animate_face_motion / animate_kv, frames of another size are a ValueError, and without an adapter that holds
+    the complete motion_encoder.* weights it is NotImplementedError.  With the
     adapter's inputs these are NotImplementedError too: a sliding window of more than one window, tea_cache,
     a VACE context, reference_latents, fuse_vae_embedding_in_latents, camera control, slg_blocks."""
+    face_pixel_values = kwargs.pop("face_pixel_values", None)
+    if face_pixel_values is not None:
+        animate_face_motion = _encode_face_pixels(animate_adapter, face_pixel_values, animate_face_motion, animate_kv)
     use_pose = pose_latents is not None or pose_tokens is not None
     use_face = animate_face_motion is not None or animate_kv is not None
-    if kwargs.get("face_pixel_values") is not None:
-        raise NotImplementedError("model_fn_wan_video: 'face_pixel_values' needs the motion encoder, which is not in "
-                                  "this build: pass the motion vectors as animate_face_motion=")
     if use_pose or use_face:
         if animate_adapter is None:
             raise ValueError("model_fn_wan_video: pose_latents / animate_face_motion need animate_adapter= (a "
@@ -1084,6 +1104,40 @@ class WanVideoPipeline:
             raise NotImplementedError(f"the animate adapter (pose_latents / animate_face_motion) with {what} is not "
                                       f"supported")
 
+    def _face_frames(self, face_video, input_video, motion, motion_uncond):
+        """animate_face_video against the rest of the call -> uint8 [T_face, size, size, 3] host frames, cut to
+        len(input_video) - 4 as WanVideoPostUnit_AnimateVideoSplit does (wan_video_new.py:1065-1080)."""
+        ad = self.animate_adapter
+        size = None if ad is None else ad.motion_size()
+        if size is None:
+            raise NotImplementedError("animate_face_video needs pipe.animate_adapter with the complete motion-encoder "
+                                      "weights (motion_encoder.* of a Wan2.2-Animate checkpoint): pass the face frames' "
+                                      "motion vectors as animate_face_motion= [T_face, 512] (and "
+                                      "animate_face_motion_uncond= with CFG)")
+        if motion is not None or motion_uncond is not None:
+            raise ValueError("pass animate_face_video or its motion vectors animate_face_motion= / "
+                             "animate_face_motion_uncond=, not both")
+        from .vae import frames_to_u8
+        frames = frames_to_u8(face_video, "cpu")
+        if input_video is not None:
+            frames = frames[:len(input_video) - 4]
+        if frames.shape[0] < 1 or tuple(frames.shape[1:3]) != (size, size):
+            raise ValueError(f"animate_face_video: face frames must be {size} x {size} (the motion encoder's size; the "
+                             f"reference does not resize them either), got {tuple(frames.shape)}")
+        return frames
+
+    def encode_face_video(self, frames, use_cfg):
+        """Face frames uint8 [T, size, size, 3] -> (animate_face_motion [T, 512], animate_face_motion_uncond
+        [512] or None): the motion encoder on the frames and, with CFG, on one constant -1 frame -- the
+        reference's negative branch sees zeros_like(face_pixel_values) - 1 and frames are independent."""
+        ad = self.animate_adapter
+        motion = ad.encode_motion(frames.to(self.device))
+        uncond = None
+        if use_cfg:
+            size = frames.shape[1]
+            uncond = ad.encode_motion(torch.full((3, 1, size, size), -1.0, device=self.device, dtype=BF16))[0]
+        return motion, uncond
+
     def _animate_kwargs(self, pose_latents, motion, motion_uncond, use_cfg, frames):
         """model_fn's Wan2.2-Animate constants, computed here once per call: the pose rows (one set for every
         CFG sample), and every fuser block's K / V from the face motion of the step's batch."""
@@ -1243,8 +1297,11 @@ class WanVideoPipeline:
         frames; or its latents pose_latents [1, 16, T' - 1, h, w]) is VAE-encoded and patch-embedded onto the
         latent frames 1..; animate_face_motion [T_face, 512] are the face frames' motion vectors (the reference's
         motion encoder output; T_face = num_frames - 4) and animate_face_motion_uncond the vector of its constant
-        -1 face frame, required with CFG.  animate_face_video itself is NotImplementedError: the motion encoder is
-        not in this build.  animate_inpaint_video + animate_mask_video (num_frames - 4 frames each) replace y by the
+        -1 face frame, required with CFG.  animate_face_video (T_face PIL images or uint8 [size, size, 3] frames at
+        the motion encoder's size, 512 for the released checkpoint; never resized) is encoded by the adapter's
+        motion encoder (vstyler.motion, adapter.encode_motion) into those vectors, the constant -1 frame with it
+        when CFG runs; it excludes animate_face_motion=, and is NotImplementedError without the complete
+        motion_encoder.* weights.  animate_inpaint_video + animate_mask_video (num_frames - 4 frames each) replace y by the
         inpaint form (animate_inpaint_y).  With both a pose and a face motion the first latent frame is dropped
         before decoding (:545-550), so the video has num_frames - 4 frames.
 
@@ -1278,12 +1335,13 @@ class WanVideoPipeline:
         of the shortened schedule (WanVideoUnit_InputVideoEmbedder, :591-614)."""
         if motion_bucket_id is not None:
             raise NotImplementedError("motion_bucket_id is outside the Ditto hot path of this build")
-        if animate_face_video is not None:
-            raise NotImplementedError("animate_face_video needs the motion encoder, which is not in this build: pass "
-                                      "the face frames' motion vectors as animate_face_motion= [T_face, 512] (and "
-                                      "animate_face_motion_uncond= with CFG)")
+        face_frames = None
+        if animate_face_video is not None:                  # WanVideoPostUnit_AnimateFacePixelValues (:1099-1108)
+            face_frames = self._face_frames(animate_face_video, input_video, animate_face_motion,
+                                            animate_face_motion_uncond)   # (encoded below, after the checks)
         has_pose = animate_pose_video is not None or pose_latents is not None
-        has_animate = has_pose or animate_face_motion is not None or animate_inpaint_video is not None or \
+        has_face = animate_face_motion is not None or face_frames is not None
+        has_animate = has_pose or has_face or animate_inpaint_video is not None or \
             animate_mask_video is not None
         if has_animate:
             if self.animate_adapter is None:
@@ -1353,6 +1411,9 @@ class WanVideoPipeline:
         if animate_pose_video is not None and pose_latents is None:           # WanVideoPostUnit_AnimatePoseLatents
             pose_latents = self.encode_animate_video(animate_pose_video, "animate_pose_video", height, width,
                                                      num_frames, tiled, tile_size, tile_stride)
+        if face_frames is not None:                         # the motion encoder, once per call
+            animate_face_motion, animate_face_motion_uncond = self.encode_face_video(
+                face_frames, any(c != 1.0 for c in scales))
         # WanVideoUnit_ImageEmbedderCLIP (wan_video_new.py:682-693); an explicit clip_feature= wins
         explicit_clip = clip_feature is not None
         if clip_feature is None and input_image is not None and self.image_encoder is not None and \
@@ -1394,7 +1455,7 @@ class WanVideoPipeline:
         self.last_tea_cache = tea_cache
         if nref:                                            # :545-550
             latents = latents[:, :, nref:].contiguous()
-        elif has_pose and animate_face_motion is not None:  # :545-550: the reference image's frame
+        elif has_pose and has_face:                         # :545-550: the reference image's frame
             latents = latents[:, :, 1:].contiguous()
         if output_type == "latents":
             return latents

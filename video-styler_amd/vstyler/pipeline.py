@@ -1,5 +1,5 @@
-"""WanVideoPipeline / model_fn_wan_video with the reference call surface
-(diffsynth/pipelines/wan_video_new.py:32-560, 1260-1468), running on libvstyler kernels.
+"""WanVideoPipeline with the reference call surface (diffsynth/pipelines/wan_video_new.py:32-560), running on
+libvstyler kernels; model_fn_wan_video (:1260-1468) is vstyler.forward's, importable from here as before.
 
 Differences from the reference that are performance-only (same per-sample arithmetic):
   * CFG runs as one batch-2 forward (posi, nega) instead of two batch-1 forwards; the per-batch
@@ -7,6 +7,7 @@ Differences from the reference that are performance-only (same per-sample arithm
   * sigma table on the host, Euler+CFG fused into one kernel (no per-step host sync);
   * Ulysses SP shards the VACE branch too (the reference runs VACE unsharded).
 """
+import functools
 import os
 from dataclasses import dataclass
 from typing import Optional, Union
@@ -15,496 +16,13 @@ import torch
 
 from . import kernels as K
 from .flow_match import FlowMatchScheduler
-from .models import IMG_TOKENS, RunCtx, Workspace, WanModel, VaceWanModel
+from .forward import (_UNSUPPORTED, _workspace, camera_token_rows, check_support,  # noqa: F401 (re-exported)
+                      model_fn_wan_video, reference_token_rows, slice_windows)
+from .models import IMG_TOKENS, WanModel, VaceWanModel
 from .options import host_option
 from .window import check_window_args, plan_windows
 
 BF16 = torch.bfloat16
-
-_WS = {}
-
-
-def _workspace(device):
-    key = str(torch.device(device))
-    if key not in _WS:
-        _WS[key] = Workspace(device)
-    return _WS[key]
-
-
-_UNSUPPORTED = ("audio_embeds", "motion_latents", "s2v_pose_latents", "motion_bucket_id")
-
-_WINDOW_PLANS = {}
-
-
-def _device_plan(device, T, size, stride):
-    """The host plan of (T, size, stride) with its masks and weight on `device`, built once."""
-    key = (str(torch.device(device)), T, size, stride)
-    if key not in _WINDOW_PLANS:
-        plan = plan_windows(T, size, stride)
-        _WINDOW_PLANS[key] = (plan, [m.to(device) for m in plan.masks], plan.weight.to(device))
-    return _WINDOW_PLANS[key]
-
-
-def slice_windows(x, plan):
-    """x[:, :, t:t_] of every window of the plan as contiguous bf16 tensors: what a caller that runs
-    many steps on one vace_context hands to model_fn_wan_video(vace_context_windows=)."""
-    x = x.to(BF16).contiguous()
-    B, C, T, H, W = x.shape
-    return [K.window_gather(x, t, torch.empty((B, C, t_ - t, H, W), device=x.device, dtype=BF16))
-            for t, t_ in plan.windows]
-
-
-def _windowed_forward(size, stride, dit, motion_controller, vace, animate_adapter, latents, vace_context,
-                      vace_context_windows, y=None, y_windows=None, **fwd):
-    """TemporalTiler_BCTHW.run (wan_video_new.py:1229-1256) around the plain forward: every window
-    [t, t_) of the latent time axis is an ordinary forward of latents[:, :, t:t_] (RoPE positions
-    0..t_-t-1, same timestep and context), blended into `value` with the window's mask and divided by
-    the accumulated weight at the end, in the reference's bf16 arithmetic (vs_window_blend /
-    vs_window_finish).  Unlike the reference, whose tiler slices only latents and y, vace_context is
-    cut with the same [t, t_): a full-length context does not match the window's tokens.  y (the image
-    conditioning channels) is cut per window as the reference's tiler does (its tensor_names list y),
-    or comes pre-cut as y_windows."""
-    device = latents.device
-    ws = _workspace(device)
-    lat = latents.to(BF16).contiguous()
-    Bl, C, T, H, W = lat.shape
-    plan, masks, weight = _device_plan(device, T, size, stride)
-    use_vace = vace_context is not None and vace is not None
-    if use_vace and vace_context_windows is None:
-        vc = vace_context.to(BF16).contiguous()
-    if y is not None and y_windows is None:
-        yc = y.to(BF16).contiguous()
-    value = None
-    for i, (t, t_) in enumerate(plan.windows):
-        lw = K.window_gather(lat, t, ws.get("win_lat", (Bl, C, t_ - t, H, W)))
-        yw = None
-        if y_windows is not None:
-            yw = y_windows[i]
-        elif y is not None:
-            yw = K.window_gather(yc, t, ws.get("win_y", (yc.shape[0], yc.shape[1], t_ - t, H, W)))
-        vw = None
-        if use_vace and vace_context_windows is not None:
-            vw = vace_context_windows[i]
-        elif use_vace:
-            vw = K.window_gather(vc, t, ws.get("win_vace", (vc.shape[0], vc.shape[1], t_ - t, H, W)))
-        out = model_fn_wan_video(dit, motion_controller, vace, animate_adapter, latents=lw, vace_context=vw, y=yw,
-                                 **fwd)
-        if value is None:
-            value = torch.zeros((out.shape[0], out.shape[1], T, H, W), device=device, dtype=BF16)
-        K.window_blend(out, masks[i], value, t)
-    return K.window_finish(value, weight)
-
-
-def _encode_face_pixels(adapter, pixels, motion, kv):
-    """model_fn's face_pixel_values [B, 3, T_face, size, size] -> animate_face_motion [B, T_face, 512] through the
-    adapter's motion encoder, sample by sample (after_patch_embedding, wan_video_animate_adapter.py:627-637)."""
-    size = None if adapter is None else adapter.motion_size()
-    if size is None:
-        raise NotImplementedError("model_fn_wan_video: 'face_pixel_values' needs animate_adapter= with the complete "
-                                  "motion-encoder weights (motion_encoder.*): pass the motion vectors as "
-                                  "animate_face_motion=")
-    if motion is not None or kv is not None:
-        raise ValueError("model_fn_wan_video: pass face_pixel_values or its motion vectors (animate_face_motion / "
-                         "animate_kv), not both")
-    if pixels.dim() != 5 or pixels.shape[1] != 3 or tuple(pixels.shape[3:]) != (size, size):
-        raise ValueError(f"model_fn_wan_video: face_pixel_values {tuple(pixels.shape)}: expected [B, 3, T_face, {size}, "
-                         f"{size}] (the motion encoder's size; the reference does not resize either)")
-    return torch.stack([adapter.encode_motion(p.to(BF16)) for p in pixels])
-
-
-def model_fn_wan_video(dit: WanModel, motion_controller=None, vace: VaceWanModel = None, animate_adapter=None,
-                       latents: torch.Tensor = None, timestep: torch.Tensor = None, context: torch.Tensor = None,
-                       vace_context=None, vace_scale=1.0, use_unified_sequence_parallel: bool = False,
-                       sp_group=None, slg_blocks=(), tea_cache=None, cfg_sample=0, sliding_window_size=None,
-                       sliding_window_stride=None, vace_context_windows=None, y=None, clip_feature=None,
-                       y_windows=None, fuse_vae_embedding_in_latents=False, reference_latents=None,
-                       control_camera_latents_input=None, reference_tokens=None, camera_tokens=None,
-                       pose_latents=None, pose_tokens=None, animate_face_motion=None, animate_kv=None, **kwargs):
-    """One DiT(+VACE) forward (wan_video_new.py:1338-1468) -> [B,dit.out_dim,T,H,W] bf16 velocity.
-
-    fuse_vae_embedding_in_latents (with dit.seperated_timestep: Wan2.2-TI2V-5B's image-to-video mode,
-    :1339-1349): latent frame 0 holds the clean first-frame latents, so its n0 = (H/2)(W/2) tokens are
-    modulated with timestep 0 and every other token with `timestep`.  The reference builds a per-token
-    [1, S, 6, dim] modulation; it has two distinct rows, so here the time embedding runs on (0,
-    bf16(timestep)) and every modulated LayerNorm and gated GEMM picks row (token >= n0) of its sample's
-    two (RunCtx.seg_rows, include/vstyler_seg.h).  One timestep for the whole batch, as the reference.
-    Not on this path (NotImplementedError): Ulysses / CFG parallelism, more than one sliding window,
-    tea_cache, a VACE module.
-
-    slg_blocks: skip-layer guidance (config 5, ComfyUI WanVideoSLG): the listed main blocks are
-    skipped for CFG sample 1 (the unconditional pass), run for sample 0 only.  cfg_sample: which
-    CFG sample a batch-1 forward computes (1: it skips the slg_blocks) -- set by the CFG-parallel
-    split below.
-
-    `context` is [B, L, text_dim]; latents/timestep/vace_context with batch 1 are broadcast to B
-    (the cfg_merge convention of wan_video_new.py:1361-1364).
-
-    sp_group may be a vstyler.usp.CfgParallel: a batch-2 (CFG) forward then runs as this rank's
-    sample only (batch 1, Ulysses over its half of the ranks) and the two samples' outputs are
-    all-gathered across the halves -- the same [2,16,T,H,W] as the batched forward.
-
-    sliding_window_size / sliding_window_stride (latent frames, both ints, 1 <= stride <= size): the
-    temporal sliding window of wan_video_new.py:1291-1315 (_windowed_forward).  stride alone is
-    ignored, as in the reference.  One window (size >= T) takes the plain path.  vace_context_windows:
-    the vace_context already cut per window (slice_windows), so a denoising loop gathers it once.
-
-    Image conditioning (wan_video_new.py:1366-1371).  y [1 or B, dit.in_dim - 16, T, H, W]: the mask +
-    VAE-encoded image channels, concatenated behind the latents when dit.require_vae_embedding (read
-    in place by the patch embedding; y_windows: y pre-cut per window).  clip_feature [1 or B, 257 or
-    514, 1280]: CLIP image features, embedded by dit.img_emb when dit.require_clip_embedding and
-    dit.has_image_input; the first 257 embedded rows are the blocks' image keys, any further rows join
-    the text keys (wan_video_dit.py:172-174).  A DiT with in_dim > 16 needs y and one with
-    has_image_input needs clip_feature: ValueError otherwise (the reference would feed the patch
-    embedding too few channels / attend to the first 257 text rows as the image).
-
-    Wan-Fun control.  reference_latents [1 or B, 16, (1,) H, W] on a has_ref_conv DiT (:1384-1390,
-    :1463-1466): dit.ref_conv turns them into n = (H/2)(W/2) tokens in front of every sample's S: the
-    forward is the ordinary one over the grid (T + 1, H/2, W/2) whose frame 0 comes from ref_conv, and the
-    head's rows n.. are unpatchified.  control_camera_latents_input [1, 24, T, 8 H, 8 W] on a DiT with
-    control_adapter (wan_video_dit.py:339-345): the adapter's output is added to the patch embedding's in
-    that GEMM's epilogue.  Neither depends on the timestep: a denoising loop computes them once
-    (reference_token_rows, camera_token_rows) and hands them over as reference_tokens [Br n, D] /
-    camera_tokens [S or B S, D], which win over the raw inputs.  ValueError: a DiT without the module, a
-    wrong shape, reference_latents together with a VACE context (the reference's token counts do not
-    match there); NotImplementedError: camera control over more than one sliding window (the reference's
-    tiler drops it, :1292-1307).
-
-    Wan2.2-Animate (animate_adapter: a WanAnimateAdapter of the DiT's width).  pose_latents [1 or B, 16,
-    T - 1, H, W]: their patch embedding is added to the tokens of latent frames 1.. in the patch-embedding
-    GEMM's epilogue (after_patch_embedding: bf16(x + bf16(pose))).  animate_face_motion [1 or B, T_face, 512]:
-    the motion vectors of the face frames (the reference's motion_encoder.get_motion output); the face
-    encoder turns them into N motion tokens per latent frame behind a zero frame, and after every fifth
-    block a FaceBlock cross-attends each frame's tokens to them (vs_face_attn).  Neither depends on the
-    timestep: a denoising loop computes them once (animate_pose_rows, animate_face_kv) and hands them over
-    as pose_tokens [S or B S, D] / animate_kv (one [B, T N, 2 D] buffer per fuser block), which win over the raw
-    inputs.  face_pixel_values [B, 3, T_face, size, size] (the reference's input, in [-1, 1]) is encoded per
-    sample by the adapter's motion encoder (encode_motion) and proceeds as animate_face_motion; it excludes
-    animate_face_motion / animate_kv, frames of another size are a ValueError, and without an adapter that holds
-    the complete motion_encoder.* weights it is NotImplementedError.  With the
-    adapter's inputs these are NotImplementedError too: a sliding window of more than one window, tea_cache,
-    a VACE context, reference_latents, fuse_vae_embedding_in_latents, camera control, slg_blocks."""
-    face_pixel_values = kwargs.pop("face_pixel_values", None)
-    if face_pixel_values is not None:
-        animate_face_motion = _encode_face_pixels(animate_adapter, face_pixel_values, animate_face_motion, animate_kv)
-    use_pose = pose_latents is not None or pose_tokens is not None
-    use_face = animate_face_motion is not None or animate_kv is not None
-    if use_pose or use_face:
-        if animate_adapter is None:
-            raise ValueError("model_fn_wan_video: pose_latents / animate_face_motion need animate_adapter= (a "
-                             "WanAnimateAdapter)")
-        if animate_adapter.dim != dit.dim or animate_adapter.num_heads != dit.num_heads or \
-                len(animate_adapter.face_adapter.fuser_blocks) != -(-len(dit.blocks) // 5):
-            raise ValueError("model_fn_wan_video: the animate adapter's dim, num_heads or fuser block count do not "
-                             "match the DiT")
-        w = check_window_args(sliding_window_size, sliding_window_stride)
-        what = ("a temporal sliding window of more than one window"
-                if w is not None and len(plan_windows(latents.shape[2], *w).windows) > 1 else
-                "tea_cache" if tea_cache is not None else
-                "a VACE context" if vace is not None and vace_context is not None else
-                "reference_latents" if reference_latents is not None or reference_tokens is not None else
-                "fuse_vae_embedding_in_latents (first_frame_latents)" if fuse_vae_embedding_in_latents else
-                "camera control" if control_camera_latents_input is not None or camera_tokens is not None else
-                "slg_blocks" if len(slg_blocks) else None)
-        if what is not None:
-            raise NotImplementedError(f"model_fn_wan_video: the animate adapter (pose_latents / animate_face_motion) "
-                                      f"with {what}")
-    use_ref = reference_latents is not None or reference_tokens is not None
-    use_cam = control_camera_latents_input is not None or camera_tokens is not None
-    if use_ref:
-        if not getattr(dit, "has_ref_conv", False):
-            raise ValueError("model_fn_wan_video: reference_latents needs a DiT with ref_conv (has_ref_conv)")
-        if vace is not None and vace_context is not None:
-            raise ValueError("model_fn_wan_video: reference_latents together with a VACE context (the reference "
-                             "tokens have no VACE rows)")
-        if reference_tokens is None:
-            reference_latents = _reference_frame(reference_latents, latents, context.shape[0])
-    if use_cam:
-        if getattr(dit, "control_adapter", None) is None:
-            raise ValueError("model_fn_wan_video: control_camera_latents_input needs a DiT with control_adapter "
-                             "(add_control_adapter)")
-        if camera_tokens is None:
-            _check_camera_input(dit, control_camera_latents_input, latents)
-    for name in _UNSUPPORTED:
-        if kwargs.get(name) is not None:
-            raise NotImplementedError(f"model_fn_wan_video: '{name}' is outside the Ditto hot path")
-    seg = bool(fuse_vae_embedding_in_latents) and bool(dit.seperated_timestep)
-    win = check_window_args(sliding_window_size, sliding_window_stride)
-    if seg:
-        what = ("Ulysses / CFG parallelism" if use_unified_sequence_parallel else
-                "a temporal sliding window of more than one window"
-                if win is not None and len(plan_windows(latents.shape[2], *win).windows) > 1 else
-                "tea_cache" if tea_cache is not None else
-                "a VACE module" if vace is not None and vace_context is not None else None)
-        if what is not None:
-            raise NotImplementedError(f"model_fn_wan_video: fuse_vae_embedding_in_latents (the first-frame "
-                                      f"segment of a seperated_timestep DiT) with {what}")
-        if timestep.numel() != 1:
-            raise ValueError("model_fn_wan_video: fuse_vae_embedding_in_latents takes one timestep for the batch")
-    if win is not None and len(plan_windows(latents.shape[2], *win).windows) > 1:
-        if tea_cache is not None:
-            # the reference hands one TeaCache state to every window (:1304), which compares and reuses
-            # residuals across different windows
-            raise NotImplementedError("model_fn_wan_video: tea_cache with a temporal sliding window")
-        if use_cam:
-            raise NotImplementedError("model_fn_wan_video: control_camera_latents_input with a temporal sliding "
-                                      "window of more than one window")
-        if use_ref and reference_tokens is None:    # the same reference rows in front of every window
-            reference_tokens = reference_token_rows(dit, reference_latents)
-        return _windowed_forward(win[0], win[1], dit, motion_controller, vace, animate_adapter, latents, vace_context,
-                                 vace_context_windows, y=y, y_windows=y_windows, clip_feature=clip_feature,
-                                 timestep=timestep, context=context, vace_scale=vace_scale,
-                                 use_unified_sequence_parallel=use_unified_sequence_parallel, sp_group=sp_group,
-                                 slg_blocks=slg_blocks, cfg_sample=cfg_sample, reference_tokens=reference_tokens,
-                                 **kwargs)
-    if y is not None and not dit.require_vae_embedding:
-        y = y_windows = None
-    use_clip = clip_feature is not None and dit.require_clip_embedding and dit.has_image_input
-    if not use_clip:
-        clip_feature = None
-    if dit.has_image_input and clip_feature is None:
-        raise ValueError("model_fn_wan_video: this DiT has the image cross-attention branch (has_image_input): "
-                         "pass clip_feature= (the CLIP image features, [1 or B, 257 or 514, 1280])")
-    if y is not None and 16 + y.shape[1] != dit.in_dim:
-        raise ValueError(f"model_fn_wan_video: y has {y.shape[1]} channels, the DiT's patch embedding takes "
-                         f"16 + {dit.in_dim - 16}")
-    if y is None and dit.in_dim > 16 and not dit.fuse_vae_embedding_in_latents:
-        raise ValueError(f"model_fn_wan_video: the DiT's patch embedding takes {dit.in_dim} channels: pass y= "
-                         f"({dit.in_dim - 16} image-conditioning channels)")
-    if use_unified_sequence_parallel:
-        from .usp import CfgParallel, get_default_group
-        plan = sp_group if sp_group is not None else get_default_group()
-        if isinstance(plan, CfgParallel):
-            if context.shape[0] != 2 or tea_cache is not None:
-                sp_group = plan.full        # no CFG pair to split (or a TeaCache step): Ulysses over all
-            else:
-                c = plan.cfg_rank
-
-                def mine(tn):
-                    return tn[c:c + 1] if tn is not None and tn.dim() > 0 and tn.shape[0] == 2 else tn
-                ts = timestep.reshape(-1)
-                hw = (latents.shape[3] // 2) * (latents.shape[4] // 2)
-                local = model_fn_wan_video(dit, motion_controller, vace, animate_adapter, latents=mine(latents),
-                                           timestep=mine(ts), context=context[c:c + 1],
-                                           vace_context=mine(vace_context), vace_scale=vace_scale,
-                                           use_unified_sequence_parallel=plan.ulysses is not None,
-                                           sp_group=plan.ulysses, slg_blocks=slg_blocks, cfg_sample=c, y=mine(y),
-                                           clip_feature=mine(clip_feature),
-                                           reference_latents=mine(reference_latents),
-                                           control_camera_latents_input=control_camera_latents_input,
-                                           reference_tokens=_mine_rows(reference_tokens, c, hw),
-                                           camera_tokens=_mine_rows(camera_tokens, c, latents.shape[2] * hw),
-                                           pose_latents=mine(pose_latents),
-                                           pose_tokens=_mine_rows(pose_tokens, c, latents.shape[2] * hw),
-                                           animate_face_motion=mine(animate_face_motion),
-                                           animate_kv=None if animate_kv is None else [mine(kv) for kv in animate_kv],
-                                           **kwargs)
-                out = torch.empty((2,) + tuple(local.shape[1:]), device=local.device, dtype=local.dtype)
-                plan.gather_cfg(out, local)
-                return out
-    device = latents.device
-    ws = _workspace(device)
-    B, L = context.shape[0], context.shape[1]
-    # every CFG sample starts from the same rows when the latents, the timestep (and the VACE context)
-    # are shared (the cfg_merge broadcast below): the first blocks' self-attention halves are then
-    # computed once for all samples (DiTBlock shared_prefix)
-    shared = B > 1 and latents.shape[0] == 1 and timestep.numel() == 1 and (y is None or y.shape[0] == 1)
-    ref = n_ref = None
-    if use_ref:
-        ref = reference_tokens if reference_tokens is not None else dit.ref_tokens(reference_latents, ws)
-        n_ref = (latents.shape[3] // 2) * (latents.shape[4] // 2)
-        if ref.dim() != 2 or ref.shape[1] != dit.dim or ref.shape[0] not in (n_ref, B * n_ref):
-            raise ValueError(f"model_fn_wan_video: reference_tokens {tuple(ref.shape)} are not [{n_ref} or "
-                             f"{B} * {n_ref}, {dit.dim}]")
-        shared = shared and ref.shape[0] == n_ref
-    shared_vace = shared and vace_context is not None and vace_context.shape[0] == 1
-    if y is not None:
-        if y.shape[0] not in (1, B) or tuple(y.shape[2:]) != tuple(latents.shape[2:]):
-            raise ValueError(f"model_fn_wan_video: y {tuple(y.shape)} does not match latents {tuple(latents.shape)} "
-                             f"(batch 1 or {B})")
-        y = y.to(device=device, dtype=BF16)
-    if clip_feature is not None and clip_feature.shape[0] not in (1, B):
-        raise ValueError(f"model_fn_wan_video: clip_feature batch {clip_feature.shape[0]} (1 or {B})")
-    if latents.shape[0] != B and y is None:
-        latents = latents.expand(B, *latents.shape[1:])
-    latents = latents.to(BF16).contiguous()
-    timestep = timestep.reshape(-1).to(device=device, dtype=BF16)
-    if timestep.shape[0] != B:
-        timestep = timestep.expand(B).contiguous()
-
-    if seg:     # (0, bf16(t)) per sample: t [2 B, D], t_mod [2 B, 6, D], rows 2 b / 2 b + 1 = b's two segments
-        timestep = torch.stack([torch.zeros_like(timestep), timestep], dim=1).reshape(-1)
-    t, t_mod = dit.time_embed(timestep, ws)
-    ctx = dit.text_embed(context.to(BF16), ws)
-    extra = {}
-    if use_cam:
-        S0 = latents.shape[2] * (latents.shape[3] // 2) * (latents.shape[4] // 2)
-        cam = camera_tokens if camera_tokens is not None else dit.control_adapter(control_camera_latents_input)
-        if cam.dim() != 2 or cam.shape[1] != dit.dim or cam.shape[0] not in (S0, B * S0):
-            raise ValueError(f"model_fn_wan_video: camera_tokens {tuple(cam.shape)} are not [{S0} or {B} * {S0}, "
-                             f"{dit.dim}]")
-        if cam.shape[0] != B * S0:      # (a loop hands the replicated rows: camera_token_rows(batch=B))
-            cam = ws.get("cam_rep", (B * S0, dit.dim)).view(B, S0, dit.dim).copy_(
-                cam.view(1, S0, dit.dim).expand(B, S0, dit.dim)).view(B * S0, dit.dim)
-        extra["residual"] = cam
-    if use_pose:
-        Tl, hw0 = latents.shape[2], (latents.shape[3] // 2) * (latents.shape[4] // 2)
-        if pose_tokens is None:
-            if tuple(pose_latents.shape[3:]) != tuple(latents.shape[3:]):
-                raise ValueError(f"model_fn_wan_video: pose_latents {tuple(pose_latents.shape)} do not match latents "
-                                 f"{tuple(latents.shape)}")
-            pose_tokens = animate_adapter.pose_rows(pose_latents, Tl, ws)
-        S0 = Tl * hw0
-        if pose_tokens.dim() != 2 or pose_tokens.shape[1] != dit.dim or pose_tokens.shape[0] not in (S0, B * S0):
-            raise ValueError(f"model_fn_wan_video: pose_tokens {tuple(pose_tokens.shape)} are not [{S0} or {B} * {S0}, "
-                             f"{dit.dim}]")
-        if pose_tokens.shape[0] != B * S0:      # one pose for every CFG sample
-            pose_tokens = ws.get("pose_rep", (B * S0, dit.dim)).view(B, S0, dit.dim).copy_(
-                pose_tokens.view(1, S0, dit.dim).expand(B, S0, dit.dim)).view(B * S0, dit.dim)
-        elif B > 1:
-            shared = False                      # per-sample rows: block 0 sees different samples
-        extra["residual"] = pose_tokens
-    if use_face:
-        if animate_kv is None:
-            if animate_face_motion.dim() != 3 or animate_face_motion.shape[0] not in (1, B):
-                raise ValueError(f"model_fn_wan_video: animate_face_motion {tuple(animate_face_motion.shape)}: expected "
-                                 f"[1 or {B}, T_face, {animate_adapter.face_encoder.in_dim}]")
-            animate_kv = animate_adapter.face_kv(animate_adapter.motion_tokens(animate_face_motion, ws), ws)
-        Tl = latents.shape[2]
-        for kv in animate_kv:
-            if kv.dim() != 3 or kv.shape[0] not in (1, B) or kv.shape[1] % Tl or not 1 <= kv.shape[1] // Tl <= 8 or \
-                    kv.shape[2] != 2 * dit.dim:
-                raise ValueError(f"model_fn_wan_video: the face motion covers {tuple(kv.shape)} key rows: expected "
-                                 f"[1 or {B}, {Tl} latent frames * N (1..8), {2 * dit.dim}] (T_face frames give "
-                                 f"((T_face - 1) // 2) // 2 + 2 latent frames)")
-    if use_ref:
-        extra["skip"] = n_ref
-    if y is None and not extra:
-        x, grid = dit.patch_embedding(latents, ws, "x")
-    elif y is None:
-        x, grid = dit.patch_embedding(latents, ws, "x", **extra)
-    else:       # cat([latents, y], dim=1) read in place; batch-1 operands broadcast over the CFG batch
-        x, grid = dit.patch_embedding(latents, ws, "x", y=y, batch=B, **extra)
-    S = grid[0] * grid[1] * grid[2]
-    if use_ref:
-        # the reference tokens are frame 0 of a grid one frame longer (wan_video_new.py:1389-1390: concat in
-        # front, RoPE for f + 1 frames): nothing below knows the difference
-        K.ref_rows(ref, x, B, n_ref, S)
-        grid, S = (grid[0] + 1, grid[1], grid[2]), n_ref + S
-    img = None
-    if clip_feature is not None:
-        # context = cat([img_emb(clip_feature), text]) split as CrossAttention.forward does: the first
-        # 257 rows are the image keys, the rest (the second image of a 514-row feature) text keys
-        emb = dit.img_embed(clip_feature.to(device), ws)
-        Bc, N, D = clip_feature.shape[0], clip_feature.shape[1], dit.dim
-        emb = emb.view(Bc, N, D)
-        img = emb[:, :IMG_TOKENS]
-        if N > IMG_TOKENS:
-            extra = N - IMG_TOKENS
-            img = ws.get("img_keys", (Bc, IMG_TOKENS, D))
-            img.copy_(emb[:, :IMG_TOKENS])
-            ctx2 = ws.get("ctx_img", (B, extra + L, D))       # built once per forward
-            ctx2[:, :extra].copy_(emb[:, IMG_TOKENS:].expand(B, extra, D))
-            ctx2[:, extra:].copy_(ctx.view(B, L, D))
-            ctx, L = ctx2.view(B * (extra + L), D), extra + L
-        img = img.reshape(Bc * IMG_TOKENS, D)
-
-    sp = None
-    if use_unified_sequence_parallel:
-        sp = sp_group
-        if sp is None:
-            from .usp import get_default_group
-            sp = get_default_group()
-        if sp is not None and sp.world_size == 1 and not getattr(sp, "force_collectives", False):
-            sp = None
-    rc = RunCtx(B, S, grid, dit.rope(device), ctx, L, ws)
-    if img is not None:
-        rc.img, rc.img_batch = img, clip_feature.shape[0]
-    if seg:
-        rc.seg_rows = grid[1] * grid[2]     # the tokens of latent frame 0 (T == 1: every row)
-
-    vace_x = None
-    if vace_context is not None and vace is not None:
-        vc = vace_context.to(BF16)
-        if vc.shape[0] != B:
-            vc = vc.expand(B, *vc.shape[1:])
-        vace_x, _ = vace.vace_patch_embedding(vc.contiguous(), ws, "vace")
-
-    # TeaCache (wan_video_new.py:1398-1402): decided on one prompt's t_mod before the blocks
-    tea_skip = tea_cache.check(dit, x, t_mod[0:1]) if tea_cache is not None else False
-    if sp is not None:
-        x, vace_x, rc = sp.shard_tokens(x, vace_x, rc)
-
-    if tea_skip:
-        tea_cache.update(x)                                     # :1418-1419 (VACE not needed)
-    else:
-        if tea_cache is not None:
-            tea_cache.begin(x)
-        hints = vace(x, vace_x, t_mod, rc, shared_prefix=shared_vace) if vace_x is not None else None
-        vmap = vace.vace_layers_mapping if hints is not None else {}
-        for i, blk in enumerate(dit.blocks):
-            # a batch-1 forward of CFG sample 1 (CFG-parallel rank) skips the slg blocks outright
-            if B == 1 and cfg_sample == 1 and i in slg_blocks:
-                continue
-            hint = hints[vmap[i]] if i in vmap else None
-            skip = B > 1 and i in slg_blocks
-            blk(x, t_mod, rc, hint=hint, hint_scale=float(vace_scale), only_batch=0 if skip else None,
-                shared_prefix=shared and i == 0)
-            if use_face:                                        # after_transformer_block
-                animate_adapter.after_block(i, x, animate_kv, rc)
-        if tea_cache is not None:
-            tea_cache.store(x)                                  # :1455-1456
-    out = dit.head(x, t, rc)
-    if sp is not None:
-        out = sp.gather_tokens(out, rc)
-    T, H2, W2 = grid
-    if use_ref:                                                 # :1464-1465: drop the reference rows
-        lat = torch.empty((B, dit.out_dim, T - 1, 2 * H2, 2 * W2), device=device, dtype=BF16)
-        return K.unpatchify_skip(out, lat, n_ref)
-    lat = torch.empty((B, dit.out_dim, T, 2 * H2, 2 * W2), device=device, dtype=BF16)
-    K.unpatchify(out, lat)
-    return lat
-
-
-def _mine_rows(rows, c, per):
-    """CFG-parallel rank c's sample of per-sample token rows ([2 per, D] -> [per, D]); shared rows pass."""
-    if rows is None or rows.shape[0] == per:
-        return rows
-    return rows[c * per:(c + 1) * per]
-
-
-def _reference_frame(reference_latents, latents, batch):
-    """reference_latents [1 or B, 16, (1,) H, W] as a [Br, 16, H, W] tensor (wan_video_new.py:1386-1387)."""
-    r = reference_latents
-    if r.dim() == 5 and r.shape[2] == 1:
-        r = r[:, :, 0]
-    want = (16,) + tuple(latents.shape[3:])
-    if r.dim() != 4 or tuple(r.shape[1:]) != want or r.shape[0] not in (1, batch):
-        raise ValueError(f"model_fn_wan_video: reference_latents {tuple(reference_latents.shape)}: expected "
-                         f"[1 or {batch}, 16, (1,) {want[1]}, {want[2]}]")
-    return r
-
-
-def _check_camera_input(dit, cc, latents):
-    T, H, W = latents.shape[2:]
-    want = (1, dit.control_adapter.in_dim, T, 8 * H, 8 * W)
-    if tuple(cc.shape) != want:
-        raise ValueError(f"model_fn_wan_video: control_camera_latents_input {tuple(cc.shape)}: expected {want}")
-
-
-def reference_token_rows(dit, reference_latents):
-    """dit.ref_conv's tokens of reference_latents [Br, 16, (1,) H, W] as a tensor of their own
-    [Br (H/2)(W/2), D]: what a denoising loop computes once and hands to every step as
-    model_fn_wan_video(reference_tokens=)."""
-    r = reference_latents[:, :, 0] if reference_latents.dim() == 5 else reference_latents
-    dev = dit.ref_conv.weight.device
-    return dit.ref_tokens(r.to(dev), _workspace(dev)).clone()
-
-
-def camera_token_rows(dit, control_camera_latents_input, batch=1):
-    """dit.control_adapter's output rows [S, D] replicated to [batch S, D]: computed once per call, the
-    residual of every step's patch-embedding GEMM (model_fn_wan_video(camera_tokens=))."""
-    rows = dit.control_adapter(control_camera_latents_input)
-    return rows if batch == 1 else rows.repeat(batch, 1)
 
 
 def fun_control_y(control_latents, y, clip_feature, in_dim, keep_clip=False):
@@ -945,8 +463,8 @@ class WanVideoPipeline:
         pipe.animate_adapter; model_fn_wan_video): computed once before the loop -- the pose rows, the face
         encoder and every fuser block's keys and values, which live in workspace buffers that the captured
         step reads and the next call overwrites.  With CFG the unconditioned sample attends the keys of
-        animate_face_motion_uncond (required then).  NotImplementedError with a sliding window, tea_cache, dit2,
-        VACE, reference_latents or first_frame_latents.
+        animate_face_motion_uncond (required then).  What does not run together (NotImplementedError) is
+        forward.EXCLUDES, checked before anything is computed (_forward_keywords).
 
         reference_latents [1, 16, (1,) h, w] / control_camera_latents_input [1, 24, T, H, W] (Wan-Fun
         control, model_fn_wan_video): neither depends on the step, so each expert's ref_conv tokens and
@@ -983,22 +501,11 @@ class WanVideoPipeline:
         from .experts import expert_cfg_scales, plan_experts
         has2 = self.dit2 is not None
         scales = expert_cfg_scales(cfg_scale, has2)
-        if has2 and tea_cache is not None:
-            # the reference hands one TeaCache state to both experts and has no coefficients for them
-            raise NotImplementedError("tea_cache_l1_thresh with a second expert (dit2) is not supported")
-        animate = pose_latents is not None or animate_face_motion is not None
-        if animate:
-            win = check_window_args(sliding_window_size, sliding_window_stride)
-            multi = win is not None and len(plan_windows(latents.shape[2], *win).windows) > 1
-            self._check_animate(multi, tea_cache, vace_context, reference_latents, first_frame_latents,
-                                control_camera_latents_input)
-        window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context,
-                                        tea_cache, y=y)
-        image_kw = self._image_kwargs(y, clip_feature)
-        self._check_control_modules(reference_latents is not None, control_camera_latents_input is not None)
-        ffl = self._first_frame(first_frame_latents, latents)
-        if ffl is not None:
-            image_kw["fuse_vae_embedding_in_latents"] = True
+        keywords, ffl = self._forward_keywords(
+            "WanVideoPipeline.denoise", latents, context_posi, context_nega, vace_context, vace_scale,
+            (sliding_window_size, sliding_window_stride), y, clip_feature, reference_latents,
+            control_camera_latents_input, tea_cache, first_frame_latents, pose_latents, animate_face_motion,
+            animate_face_motion_uncond)
         self.scheduler.set_timesteps(num_inference_steps, denoising_strength=denoising_strength, shift=sigma_shift)
         n_steps = len(self.scheduler.timesteps)
         segments = plan_experts(self.scheduler.timesteps, switch_DiT_boundary, has2)
@@ -1013,26 +520,13 @@ class WanVideoPipeline:
         ts = self.scheduler.timesteps.to(dtype=BF16).to(self.device)                     # :526
         ds = torch.tensor([self.scheduler.delta(i) for i in range(n_steps)], dtype=torch.float32,
                           device=self.device)
-        ctx_cfg = None
 
-        def make_step(dit, vace, scale):
-            nonlocal ctx_cfg
+        def make_step(e, scale):
             use_cfg = scale != 1.0
-            if use_cfg and ctx_cfg is None:
-                ctx_cfg = torch.cat([context_posi, context_nega], 0)
-            ctx = ctx_cfg if use_cfg else context_posi
-            control_kw = self._control_kwargs(dit, reference_latents, control_camera_latents_input,
-                                              2 if use_cfg else 1)
-            if animate:
-                control_kw.update(self._animate_kwargs(pose_latents, animate_face_motion, animate_face_motion_uncond,
-                                                       use_cfg, latents.shape[2]))
+            kw = keywords(e, use_cfg)       # the expert's constants: computed here, outside any capture
 
             def step(t_buf, d_buf):
-                v = self.model_fn(dit=dit, vace=vace, latents=latents, timestep=t_buf, context=ctx,
-                                  vace_context=vace_context, vace_scale=vace_scale,
-                                  use_unified_sequence_parallel=self.use_unified_sequence_parallel,
-                                  sp_group=self.sp_group, tea_cache=tea_cache, **window_kw, **image_kw,
-                                  **control_kw)
+                v = self.model_fn(latents=latents, timestep=t_buf, **kw)
                 K.cfg_euler_dev(v[0:1], v[1:2] if use_cfg else None, latents, scale, d_buf)
                 if ffl is not None:
                     latents[:, :, 0:1].copy_(ffl)                                        # :541-542
@@ -1045,10 +539,9 @@ class WanVideoPipeline:
         steppers = []
         stream = None
         for first, last, e in segments:
-            dit, vace = self._expert(e)
             seg_graph = use_graph and last > first
             comms = plan_native_comms(plan) if plan is not None and seg_graph else ()
-            st = DenoiseStepper(make_step(dit, vace, scales[e - 1]), ts, ds, seg_graph, comms=comms, plan=plan,
+            st = DenoiseStepper(make_step(e, scales[e - 1]), ts, ds, seg_graph, comms=comms, plan=plan,
                                 stream=stream)
             stream = st.stream if st.stream is not None else stream
             steppers += [st] * (last - first + 1)
@@ -1065,12 +558,9 @@ class WanVideoPipeline:
         """first_frame_latents= of denoise as a device bf16 [1, C, 1, h, w] tensor (None without)."""
         if first_frame_latents is None:
             return None
-        dit = self.dit
-        if dit is None or not (dit.fuse_vae_embedding_in_latents and dit.seperated_timestep):
+        if self.dit is None or not (self.dit.fuse_vae_embedding_in_latents and self.dit.seperated_timestep):
             raise ValueError("first_frame_latents needs a DiT with fuse_vae_embedding_in_latents and "
                              "seperated_timestep (Wan2.2-TI2V-5B)")
-        if self.dit2 is not None:
-            raise NotImplementedError("first_frame_latents with a second expert (dit2) is not supported")
         want = (1, latents.shape[1], 1) + tuple(latents.shape[3:])
         if tuple(first_frame_latents.shape) != want:
             raise ValueError(f"first_frame_latents: expected {want}, got {tuple(first_frame_latents.shape)}")
@@ -1088,21 +578,72 @@ class WanVideoPipeline:
                 raise ValueError("camera control needs a DiT with control_adapter (add_control_adapter); with two "
                                  "experts, both")
 
-    def _check_animate(self, windows, tea_cache, vace_context, reference_latents, first_frame_latents,
-                       control_camera_latents_input):
-        """The Wan2.2-Animate inputs of a loop against the rest of the call, before anything is computed."""
-        if self.animate_adapter is None:
+    def _forward_keywords(self, who, latents, context_posi, context_nega, vace_context, vace_scale, window, y,
+                          clip_feature, reference_latents, control_camera_latents_input, tea_cache=None,
+                          first_frame_latents=None, pose_latents=None, animate_face_motion=None,
+                          animate_face_motion_uncond=None):
+        """What a sampler (`who`) hands to self.model_fn beside latents and timestep -> (keywords, ffl).
+
+        Once per call, here: the support matrix (forward.check_support) and the module checks, before anything is
+        computed; then the window keywords (window = (size, stride); vace_context and y are cut per window once),
+        the image keywords as device bf16 tensors and the first-frame flag.  keywords(e, use_cfg) adds expert e's
+        dit / vace, the context of the step's batch and that expert's Wan-Fun and Animate constants; they are
+        computed at the first call for (e, use_cfg) and kept.  ffl: _first_frame's tensor."""
+        win = check_window_args(*window)
+        plan = None if win is None else plan_windows(latents.shape[2], *win)        # the call's one plan
+        windows = plan is not None and len(plan.windows) > 1
+        animate = pose_latents is not None or animate_face_motion is not None
+        use_vace = vace_context is not None and (self.vace is not None or
+                                                 (self.dit2 is not None and self.vace2 is not None))
+        check_support({"animate": animate, "first_frame": first_frame_latents is not None, "windows": windows,
+                       "tea_cache": tea_cache is not None, "vace": use_vace, "reference": reference_latents is not None,
+                       "camera": control_camera_latents_input is not None, "dit2": self.dit2 is not None,
+                       "sp": bool(self.use_unified_sequence_parallel)}, who)
+        if animate and self.animate_adapter is None:
             raise ValueError("pose_latents / animate_face_motion need pipe.animate_adapter (a Wan2.2-Animate checkpoint)")
-        what = ("a temporal sliding window" if windows else
-                "tea_cache" if tea_cache is not None else
-                "a second expert (dit2)" if self.dit2 is not None else
-                "VACE" if vace_context is not None and self.vace is not None else
-                "reference_latents" if reference_latents is not None else
-                "first_frame_latents" if first_frame_latents is not None else
-                "camera control" if control_camera_latents_input is not None else None)
-        if what is not None:
-            raise NotImplementedError(f"the animate adapter (pose_latents / animate_face_motion) with {what} is not "
-                                      f"supported")
+        self._check_control_modules(reference_latents is not None, control_camera_latents_input is not None)
+        ffl = self._first_frame(first_frame_latents, latents)
+        common = dict(vace_context=vace_context, vace_scale=vace_scale, tea_cache=tea_cache,
+                      use_unified_sequence_parallel=self.use_unified_sequence_parallel, sp_group=self.sp_group)
+        if win is not None:
+            common.update(sliding_window_size=win[0], sliding_window_stride=win[1])
+        if windows and use_vace:
+            common["vace_context_windows"] = slice_windows(vace_context.to(self.device), plan)
+        if windows and y is not None:
+            common["y_windows"] = slice_windows(y.to(self.device), plan)
+        if y is not None:
+            common["y"] = y.to(device=self.device, dtype=BF16).contiguous()
+        if clip_feature is not None:
+            common["clip_feature"] = clip_feature.to(device=self.device, dtype=BF16).contiguous()
+        if ffl is not None:
+            common["fuse_vae_embedding_in_latents"] = True
+        ctx_cfg = None
+
+        @functools.lru_cache(maxsize=None)      # an expert's constants are computed at its first step and kept
+        def keywords(e, use_cfg):
+            nonlocal ctx_cfg
+            dit, vace = self._expert(e)
+            if use_cfg and ctx_cfg is None:
+                ctx_cfg = torch.cat([context_posi, context_nega], 0)
+            kw = dict(common, dit=dit, vace=vace, context=ctx_cfg if use_cfg else context_posi)
+            # Wan-Fun: the expert's ref_conv tokens, its camera adapter rows replicated over the step's batch
+            if reference_latents is not None:
+                kw["reference_tokens"] = reference_token_rows(dit, reference_latents.to(self.device))
+            if control_camera_latents_input is not None:
+                kw["camera_tokens"] = camera_token_rows(dit, control_camera_latents_input.to(self.device),
+                                                        2 if use_cfg else 1)
+            # Wan2.2-Animate: the pose rows (one set for every CFG sample), every fuser block's K / V from the
+            # face motion of the step's batch
+            if animate:
+                ad, ws = self.animate_adapter, _workspace(self.device)
+                kw["animate_adapter"] = ad
+            if pose_latents is not None:
+                kw["pose_tokens"] = ad.pose_rows(pose_latents.to(self.device), latents.shape[2], ws)
+            if animate_face_motion is not None:
+                m = animate_face_motion_batch(animate_face_motion.to(self.device), animate_face_motion_uncond, use_cfg)
+                kw["animate_kv"] = ad.face_kv(ad.motion_tokens(m, ws), ws)
+            return kw
+        return keywords, ffl
 
     def _face_frames(self, face_video, input_video, motion, motion_uncond):
         """animate_face_video against the rest of the call -> uint8 [T_face, size, size, 3] host frames, cut to
@@ -1138,54 +679,6 @@ class WanVideoPipeline:
             uncond = ad.encode_motion(torch.full((3, 1, size, size), -1.0, device=self.device, dtype=BF16))[0]
         return motion, uncond
 
-    def _animate_kwargs(self, pose_latents, motion, motion_uncond, use_cfg, frames):
-        """model_fn's Wan2.2-Animate constants, computed here once per call: the pose rows (one set for every
-        CFG sample), and every fuser block's K / V from the face motion of the step's batch."""
-        ad, ws = self.animate_adapter, _workspace(self.device)
-        kw = {"animate_adapter": ad}
-        if pose_latents is not None:
-            kw["pose_tokens"] = ad.pose_rows(pose_latents.to(self.device), frames, ws)
-        if motion is not None:
-            m = animate_face_motion_batch(motion.to(self.device), motion_uncond, use_cfg)
-            kw["animate_kv"] = ad.face_kv(ad.motion_tokens(m, ws), ws)
-        return kw
-
-    def _control_kwargs(self, dit, reference_latents, control_camera_latents_input, batch):
-        """model_fn's Wan-Fun constants of one expert ({} without them): its ref_conv tokens and its camera
-        adapter rows replicated over the step's batch, computed here once."""
-        kw = {}
-        if reference_latents is not None:
-            kw["reference_tokens"] = reference_token_rows(dit, reference_latents.to(self.device))
-        if control_camera_latents_input is not None:
-            kw["camera_tokens"] = camera_token_rows(dit, control_camera_latents_input.to(self.device), batch)
-        return kw
-
-    def _image_kwargs(self, y, clip_feature):
-        """model_fn's image-conditioning arguments as device bf16 tensors ({} without them)."""
-        kw = {}
-        if y is not None:
-            kw["y"] = y.to(device=self.device, dtype=BF16).contiguous()
-        if clip_feature is not None:
-            kw["clip_feature"] = clip_feature.to(device=self.device, dtype=BF16).contiguous()
-        return kw
-
-    def _window_kwargs(self, T, size, stride, vace_context, tea_cache=None, y=None):
-        """model_fn's sliding-window arguments for a loop over T latent frames ({} without windows)."""
-        win = check_window_args(size, stride)
-        if win is None:
-            return {}
-        kw = dict(sliding_window_size=win[0], sliding_window_stride=win[1])
-        plan = plan_windows(T, *win)
-        if len(plan.windows) > 1:
-            if tea_cache is not None:
-                raise NotImplementedError("tea_cache_l1_thresh with a temporal sliding window is not supported")
-            if vace_context is not None and (self.vace is not None or
-                                             (self.dit2 is not None and self.vace2 is not None)):
-                kw["vace_context_windows"] = slice_windows(vace_context.to(self.device), plan)
-            if y is not None:
-                kw["y_windows"] = slice_windows(y.to(self.device), plan)
-        return kw
-
     def denoise_unipc(self, latents, context_posi, context_nega, vace_context=None, vace_scale=1.0,
                       cfg_scale=1.2, num_inference_steps=4, sigma_shift=2.0, slg_blocks=(), slg_range=(0.2, 0.7),
                       progress_bar_cmd=None, input_latents=None, forward_step=None, skip_backward_step=None,
@@ -1219,11 +712,11 @@ class WanVideoPipeline:
             raise ValueError("first_frame_latents is not supported by the UniPC sampler (use denoise)")
         has2 = self.dit2 is not None
         scales = expert_cfg_scales(cfg_scale, has2)
-        window_kw = self._window_kwargs(latents.shape[2], sliding_window_size, sliding_window_stride, vace_context,
-                                        y=y)
-        window_kw.update(self._image_kwargs(y, clip_feature))       # (y / clip_feature: as in denoise)
-        self._check_control_modules(reference_latents is not None, control_camera_latents_input is not None)
-        control_kw = {}     # (expert, batch) -> the Wan-Fun constants, computed at that expert's first step
+        # (y / clip_feature: as in denoise; the Wan-Fun constants are computed at each expert's first step)
+        keywords, _ = self._forward_keywords(
+            "WanVideoPipeline.denoise_unipc", latents, context_posi, context_nega, vace_context, vace_scale,
+            (sliding_window_size, sliding_window_stride), y, clip_feature, reference_latents,
+            control_camera_latents_input)
         from .unipc import FlowUniPCMultistepScheduler, cast
         sched = FlowUniPCMultistepScheduler(shift=1.0)
         sched.set_timesteps(num_inference_steps, shift=sigma_shift)
@@ -1241,8 +734,6 @@ class WanVideoPipeline:
         for lo, hi, e in plan_experts(sched.timesteps[first:], switch_DiT_boundary, has2):
             for i in range(first + lo, first + hi + 1):
                 expert_of[i] = e
-        any_cfg = any(scales[e - 1] != 1.0 for e in expert_of.values())
-        ctx_cfg = torch.cat([context_posi, context_nega], 0) if any_cfg else None
         lat32 = latents.to(device=self.device, dtype=torch.float32).contiguous().clone()
         if input_latents is not None:
             x0 = input_latents.to(device=self.device, dtype=torch.float32).contiguous()
@@ -1258,18 +749,10 @@ class WanVideoPipeline:
             cast(lat32, lat16)
             frac = i / n
             slg = tuple(slg_blocks) if slg_range[0] <= frac <= slg_range[1] else ()
-            dit, vace = self._expert(expert_of[i])
             scale = scales[expert_of[i] - 1]
             use_cfg = scale != 1.0
-            ctx = ctx_cfg if use_cfg else context_posi
-            ck = (expert_of[i], use_cfg)
-            if ck not in control_kw:
-                control_kw[ck] = self._control_kwargs(dit, reference_latents, control_camera_latents_input,
-                                                      2 if use_cfg else 1)
-            v = self.model_fn(dit=dit, vace=vace, latents=lat16, timestep=t.reshape(1).to(
-                dtype=BF16, device=self.device), context=ctx, vace_context=vace_context, vace_scale=vace_scale,
-                use_unified_sequence_parallel=self.use_unified_sequence_parallel, sp_group=self.sp_group,
-                slg_blocks=slg, **window_kw, **control_kw[ck])
+            v = self.model_fn(latents=lat16, timestep=t.reshape(1).to(dtype=BF16, device=self.device),
+                              slg_blocks=slg, **keywords(expert_of[i], use_cfg))
             v16.zero_()
             K.cfg_euler(v[0:1], v[1:2] if use_cfg else None, v16, scale, 1.0)   # v16 = cfg combine
             cast(v16, v32)
@@ -1373,8 +856,8 @@ class WanVideoPipeline:
         check_window_args(sliding_window_size, sliding_window_stride)
         from .experts import expert_cfg_scales
         scales = expert_cfg_scales(cfg_scale, self.dit2 is not None)
-        if tea_cache_l1_thresh is not None and self.dit2 is not None:
-            raise NotImplementedError("tea_cache_l1_thresh with a second expert (dit2) is not supported")
+        # (denoise checks the whole call; this pair here, before anything is encoded)
+        check_support({"tea_cache": tea_cache_l1_thresh is not None, "dit2": self.dit2 is not None}, "WanVideoPipeline")
         height, width, num_frames = self.check_resize_height_width(height, width, num_frames, output_type)
         T = (num_frames - 1) // 4 + 1
         zc, zs = self.latent_geometry(output_type)
